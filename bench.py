@@ -6,6 +6,11 @@ One "step" = one pass of the MD loop body (reference src/main.F90:64-98: kick, d
 kick) over the workload, inputs resident in HBM.  Workload at N=1 = BASELINE.json configs[1]: RDX unit cell
 (168 atoms) replicated 18x18x18 = 979,776 atoms, QEq tol 1e-7, dt 0.25 fs, v0 = 0, q0 = 0 (the reference's
 own example input, examples/1-reaxff/rxmd.in).  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set-up, --warmup steps, --steps timed steps, the result line.  --full adds everything else the
+benchmark measures: the CPU baseline (the reference on the host cores), the matrix-value read probe, the other QEq algebra, the steady-state leg,
+isQEq 2, the placement-search and bond-stream legs and the other BASELINE configurations (each still switched off by its own --no-* flag).
+--dump-outputs DIR writes what the timed path left a caller after its last step as DIR/<name>.npy (float64; see dump_outputs).
 """
 import argparse, json, os, resource, shutil, subprocess, sys, tempfile, time
 
@@ -17,6 +22,8 @@ L2_PEAK_GBS = 34500.0  # aggregate L2 -> L1 rate of the 8 XCDs, same guide
 ATOMIC_REQ_PER_S = 20e9  # scattered float atomics at the memory side: 0.08 TB/s of 4-byte adds, one 64-byte request each (same guide)
 SIMDS, CLOCK_HZ = 1024, 2.4e9   # 256 CUs x 4 SIMDs, peak engine clock: a wave64 vector instruction occupies its SIMD for 4 cycles
 ATOMS_PER_GPU_CELLS = 18
+DUMP_SAMPLE_ATOMS = 262144      # --dump-outputs: above this many atoms a fixed sample of them (11 doubles each: 23 MB)
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
 
 
 def _run_reference(exe, gen, mc, nsteps, nthreads):
@@ -196,6 +203,43 @@ def compact_leg(workload, ncells, steps, warmup, device, **kw):
         eng.close()
 
 
+def dump_sample_mask(gid, natoms_total):
+    """the atoms --dump-outputs keeps: all of them up to DUMP_SAMPLE_ATOMS, above that a fixed pseudo-random sample chosen by a seeded hash of the
+    global id alone -- the same atoms from run to run and on every rank grid, whichever rank owns them"""
+    import numpy as np
+    if natoms_total <= DUMP_SAMPLE_ATOMS:
+        return np.ones(len(gid), bool)
+    h = ((np.asarray(gid, np.uint64) + np.uint64(12345)) * np.uint64(2654435761)) % np.uint64(2 ** 32)
+    return h < np.uint64(int(2 ** 32 * DUMP_SAMPLE_ATOMS / natoms_total))
+
+
+def dump_outputs(out_dir, eng, en, natoms_total, rank, world, gather=None):
+    """--dump-outputs: what the timed path (RxmdEngine.step) leaves a caller after its last step -- the atoms (RxmdEngine.atoms(): global id,
+    position, velocity, force, charge; in global-id order, a fixed sample above DUMP_SAMPLE_ATOMS atoms, every rank's share gathered on rank 0)
+    and the energies (RxmdEngine.energy() of rank 0) -- as out_dir/<name>.npy, float64, DUMP_LIMIT_BYTES at most"""
+    import numpy as np
+    a = eng.atoms()
+    keep = dump_sample_mask(a["gid"], natoms_total)
+    part = {k: a[k][keep] for k in ("gid", "pos", "v", "f", "q")}
+    if world > 1:
+        parts = gather(part)
+        if rank != 0:
+            return None
+        part = {k: np.concatenate([p[k] for p in parts]) for k in part}
+    order = np.argsort(part["gid"], kind="stable")
+    arrays = {"gid": part["gid"][order].astype(np.float64), "pos": part["pos"][order], "v": part["v"][order], "f": part["f"][order],
+              "q": part["q"][order], "pe": np.asarray(en["PE"], np.float64), "ke": np.array([en["KE"]]), "qsum": np.array([en["qsum"]]),
+              "astr": np.asarray(en["astr"], np.float64)}
+    arrays = {k: np.ascontiguousarray(v, np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes, more than %d" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return {"dir": out_dir, "atoms": len(order), "of": natoms_total, "bytes": total}
+
+
 def spawn_ranks(n):
     """start `n` ranks of this script under torch.distributed.run as a child process; returns its exit code"""
     import socket
@@ -345,6 +389,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--cells", type=int, default=ATOMS_PER_GPU_CELLS, help="RDX unit cells per edge per GPU (18 -> 979,776 atoms)")
+    ap.add_argument("--full", action="store_true", help="also run every other measurement: CPU baseline, read probe, the alt / steady / isQEq 2 / "
+                    "placement / bond-stream legs and the other BASELINE configurations (each can still be switched off by its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed (atoms in global-id order, a fixed sample above %d atoms; energies) "
+                         "as DIR/<name>.npy, float64" % DUMP_SAMPLE_ATOMS)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--qeq-mode", type=int, default=1, help="1: one matrix pass per CG iteration (gradient by recurrence; default), 0: the reference's two passes")
     ap.add_argument("--no-alt", action="store_true", help="skip the second leg (the other qeq_mode over the SAME trajectory window, reported under \"alt\")")
@@ -359,6 +408,8 @@ def main():
                     help="write the FULL record (per-kernel roofline table, every leg with its breakdown) to FILE; the line on stdout is its compact form, "
                          "kept under 8 KB so that a driver that records the tail of stdout sees all of it (default: the full record goes to stderr)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # `python bench.py --gpus N` without a launcher (the reference is started as `mpirun -np N rxmd`, examples/2-reaxff-dc/Makefile): this
     # process touches neither torch nor HIP; it starts the N ranks as a CHILD (torch.distributed.run, one rank per GPU), relays what they
@@ -368,7 +419,7 @@ def main():
         # the record to rank 0 through a file, so that an N > 1 line carries `cpu_baseline` like the N = 1 line does (the reference prints its
         # timer table on every rank count, main.F90:135-182)
         tmpf = None
-        if not a.no_cpu_baseline and a.workload == "rdx":
+        if a.full and not a.no_cpu_baseline and a.workload == "rdx":
             cbp = cpu_baseline(a.cpu_baseline_sample)
             if cbp is not None:
                 fd, tmpf = tempfile.mkstemp(prefix="rxmd_cpu_baseline_", suffix=".json")
@@ -389,9 +440,9 @@ def main():
 
     # the CPU baseline first: rank 0 of a 1-GPU run, before torch / HIP exist in this process
     cb = None
-    if not a.no_cpu_baseline and int(os.environ.get("WORLD_SIZE", "1")) == 1 and a.workload == "rdx" and "RXMD_BENCH_FORCE_DIST" not in os.environ:
+    if a.full and not a.no_cpu_baseline and int(os.environ.get("WORLD_SIZE", "1")) == 1 and a.workload == "rdx" and "RXMD_BENCH_FORCE_DIST" not in os.environ:
         cb = cpu_baseline(a.cpu_baseline_sample)
-    elif os.environ.get("RXMD_BENCH_CPU_BASELINE_FILE") and int(os.environ.get("RANK", "0")) == 0:
+    elif a.full and os.environ.get("RXMD_BENCH_CPU_BASELINE_FILE") and int(os.environ.get("RANK", "0")) == 0:
         try:                                  # measured by the parent of a self-spawned N > 1 run (above)
             cb = json.load(open(os.environ["RXMD_BENCH_CPU_BASELINE_FILE"]))
             cb["measured_by"] = "the parent process of bench.py --gpus N, before it started the ranks"
@@ -504,6 +555,18 @@ def main():
         dt = float(t.item())
     st = eng.stats()
     en = eng.energy()
+    dumped = None
+    if a.dump_outputs:                           # before any other leg touches the engine's state
+        if world > 1 and not a.replicas:
+            def gather(obj):
+                got = [None] * world if rank == 0 else None
+                dist.gather_object(obj, got, dst=0)
+                return got
+            dumped = dump_outputs(a.dump_outputs, eng, en, natoms * world, rank, world, gather)
+        elif rank == 0:                          # one rank, or independent replicas: rank 0's own system
+            dumped = dump_outputs(a.dump_outputs, eng, en, natoms, 0, 1)
+        if dumped:
+            sys.stderr.write("bench.py: outputs of the last timed step: %(atoms)d of %(of)d atoms, %(bytes)d bytes in %(dir)s\n" % dumped)
     per_rank = None
     if use_dist:          # every rank's residents, ghosts, CG iterations and exchange timers: a decomposition that silently lost a neighbour, or a rank
         # that waits for its halo, shows here
@@ -522,7 +585,7 @@ def main():
         for j, k in enumerate(("place_ms_first", "place_ms_kept", "place_draws", "pass_ms_in_the_loop")):
             per_rank[k] = [round(float(t[4 + len(tkeys) + j]), 4) for t in allr]
     probe = None
-    if world == 1:                               # plain 16-B/lane read of the matrix value array on this very box: the ceiling the pass is quoted next to
+    if a.full and world == 1:                    # plain 16-B/lane read of the matrix value array on this very box: the ceiling the pass is quoted next to
         try:
             pr = eng.debug(12, cap=16)
             rates = [pr[2 * g + 1] / (pr[2 * g] * 1e-3) / 1e9 for g in range(4) if pr[2 * g] > 0]
@@ -530,7 +593,7 @@ def main():
         except Exception:
             probe = None
     alt = None
-    if not a.no_alt and world == 1:
+    if a.full and not a.no_alt and world == 1:
         # the other QEq algebra over the SAME window: restart from the same initial records, same warm-up, same number of steps (the
         # reference's exit test makes the iteration count jump from step to step, so only equal windows compare)
         eng.set_qeq_mode(1 - a.qeq_mode)
@@ -549,7 +612,7 @@ def main():
         eng.set_qeq_mode(a.qeq_mode)
 
     steady = None
-    if not a.no_steady and world == 1:
+    if a.full and not a.no_steady and world == 1:
         # SURVEY 8(d) protocol: 100 timed steps after 10 warm-up steps from the same cold start (q0 = 0, v0 = 0).  The headline window (--steps after
         # --warmup) sits in the first steps, where the charges start from zero and the CG needs ~36 iterations per step; here it has settled (K ~ 24).
         eng.set_atoms_rxff(rec)
@@ -567,7 +630,7 @@ def main():
                   "breakdown_ms_per_step": {k: ss[k] / 100 for k in ("ms_qeq", "ms_qeq_spmv", "ms_lists", "ms_force", "ms_bo", "ms_nonbond", "ms_bonded", "ms_k_winbuild")}}
 
     other, alt_lex, noplace, one_stream = None, None, None, None
-    if world == 1 and not a.no_other_configs and a.workload == "rdx" and a.cells == ATOMS_PER_GPU_CELLS:
+    if a.full and world == 1 and not a.no_other_configs and a.workload == "rdx" and a.cells == ATOMS_PER_GPU_CELLS:
         eng.close(); eng = None                                   # the 979,776-atom engine gives its memory back first
         # isQEq = 2 (qeq.F90:51-57, main.F90:67-68,98): the reference's own production mode -- extended-Lagrangian charges, ONE CG step per MD
         # step; there the non-CG part of the step IS the step

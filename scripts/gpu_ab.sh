@@ -1,6 +1,6 @@
 # generic A/B of env toggles on the default bench: usage  [BENCH_ARGS="..."] bash scripts/gpu_ab.sh "ENV1=1" "ENV2=1 ENV3=0" ...   (each run twice, interleaved, under a time limit)
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
-ARGS=${BENCH_ARGS:---no-cpu-baseline --steps 8 --warmup 2 --no-alt}
+ARGS=${BENCH_ARGS:---full --no-cpu-baseline --steps 8 --warmup 2 --no-alt}
 for rep in 1 2; do
 for v in "$@"; do
   env $v timeout -k 10 600 python3 bench.py $ARGS 2>&1 | grep '^{"metric' | python3 -c "

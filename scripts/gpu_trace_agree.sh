@@ -5,7 +5,7 @@
 # usage: bash scripts/gpu_trace_agree.sh <tag>
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 O=gpurun_out/$1; mkdir -p $O
-RXMD_PLACE_TRIES=1 timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --no-cpu-baseline --no-other-configs --no-alt --full-line $O/bench_full.json > $O/bench.log 2>&1
+RXMD_PLACE_TRIES=1 timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --full --no-cpu-baseline --no-other-configs --no-alt --full-line $O/bench_full.json > $O/bench.log 2>&1
 python3 - <<PY
 import csv, glob, json
 d = json.load(open("$O/bench_full.json")); r = d["roofline"]

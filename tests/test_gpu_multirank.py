@@ -320,7 +320,7 @@ def test_bench_launches_eight_ranks_on_the_2x2x2_grid_and_carries_the_cpu_baseli
     env = dict(os.environ, RXMD_BENCH_BACKEND="gloo", RXMD_BENCH_DEVICE="0", RXMD_SINGLE_STREAM="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "RXMD_BENCH_CPU_BASELINE_FILE"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--cells", "3", "--steps", "2", "--warmup", "1", "--cpu-baseline-sample", "small"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--cells", "3", "--steps", "2", "--warmup", "1", "--full", "--cpu-baseline-sample", "small"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     r = json.loads([l for l in p.stdout.split("\n") if l.startswith("{")][-1])

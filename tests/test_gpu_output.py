@@ -154,3 +154,29 @@ def test_device_resident_minimiser_against_the_references_line_search_and_the_or
     # minimised structure (rms 0.55 kcal/mol/A) that is 4e-7 absolute = 1.4e-6 of the rms (measured)
     assert (np.abs(a["f"] - fo).max(axis=1) / np.maximum(np.abs(fo).max(axis=1), frms)).max() <= 5e-6
     e.close()
+
+
+def test_plain_bench_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: the headline leg alone (no CPU baseline, no other legs), K timed steps, and
+    what the last timed step left a caller -- atoms in global-id order, energies -- as DIR/<name>.npy in float64"""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    out = tmp_path / "out"
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--cells", "3", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    r = json.loads([l for l in p.stdout.split("\n") if l.startswith("{")][-1])
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["unit"] == "steps/s" and r["higher_is_better"] is True and r["dtype"] == "f64"
+    assert r["value"] > 0 and abs(r["value"] * r["ms_per_step"] - 1e3) < 1e-6 * 1e3
+    assert "cpu_baseline" not in r and [l["leg"] for l in r["legs"]] == ["headline"]
+    got = {f[:-4]: np.load(str(out / f)) for f in os.listdir(str(out))}
+    assert sorted(got) == ["astr", "f", "gid", "ke", "pe", "pos", "q", "qsum", "v"]
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in got.values())
+    n = 168 * 27
+    assert got["gid"].shape == (n,) and len(np.unique(got["gid"])) == n and (np.diff(got["gid"]) > 0).all()
+    assert got["pos"].shape == got["v"].shape == got["f"].shape == (n, 3) and got["q"].shape == (n,) and got["pe"].shape == (14,)
+    assert abs(got["q"].sum() - got["qsum"][0]) < 1e-8 and np.abs(got["v"]).max() > 0
+    assert abs(got["pe"][0] / n - r["energy_per_atom"]["PE"]) <= 1e-12 * abs(r["energy_per_atom"]["PE"])

@@ -290,3 +290,24 @@ def test_bench_line_stays_under_the_drivers_tail_and_ends_with_the_legs():
     assert p2["ms_per_step"] < p4["ms_per_step"] < p8["ms_per_step"] and p2["self_loop_part_ms"] == p8["self_loop_part_ms"]
     assert abs(p8["wire_ms"] - 3 * p2["wire_ms"]) < 2e-3 and p8["vector_halo_exposed_ms_per_iteration"] == 0.0
     assert bench.predict_ms_per_step((2, 2, 2), 36.55, 400262, 0.10)["vector_halo_exposed_ms_per_iteration"] > 0.0
+
+
+def test_bench_dump_sample_is_fixed_and_fits_the_limit():
+    """--dump-outputs keeps every atom of a small system and, above DUMP_SAMPLE_ATOMS, the same hash-chosen sample of global ids on every run and
+    every rank grid (a rank's share is the sample restricted to its ids); --steps below 1 is refused before anything runs"""
+    import subprocess, sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.dump_sample_mask(np.arange(1, 4537), 4536).all()
+    n = 168 * 18 ** 3
+    gid = np.arange(1, n + 1)
+    m = bench.dump_sample_mask(gid, n)
+    assert abs(int(m.sum()) - bench.DUMP_SAMPLE_ATOMS) < 0.02 * bench.DUMP_SAMPLE_ATOMS
+    assert np.array_equal(m, bench.dump_sample_mask(gid, n))
+    perm = np.random.default_rng(1).permutation(gid)
+    assert np.array_equal(np.sort(perm[bench.dump_sample_mask(perm, n)]), gid[m])
+    assert int(m.sum()) * 11 * 8 < bench.DUMP_LIMIT_BYTES
+    env = dict(os.environ); env.pop("WORLD_SIZE", None)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    assert p.returncode != 0 and "--steps" in p.stderr and "{" not in p.stdout
