@@ -181,6 +181,31 @@ module rxmd_hip_mod
        type(c_ptr), value :: h
        real(c_double), intent(out) :: ke, qsum, pe(0:13), astr6(6)
      end function
+     ! variable cell (no counterpart in the reference: its box is fixed after INITSYSTEM)
+     integer(c_int) function rxmd_hip_set_lattice(h, lat) bind(c, name='rxmd_hip_set_lattice')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: h
+       real(c_double), intent(in) :: lat(6)
+     end function
+     integer(c_int) function rxmd_hip_get_lattice(h, lat) bind(c, name='rxmd_hip_get_lattice')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: h
+       real(c_double), intent(out) :: lat(6)
+     end function
+     integer(c_int) function rxmd_hip_set_barostat(h, mode, axes, p0_GPa, tau_fs, bulk_modulus_GPa, every, max_strain) &
+         bind(c, name='rxmd_hip_set_barostat')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: h
+       integer(c_int), value :: mode, axes, every
+       real(c_double), intent(in) :: p0_GPa(3)
+       real(c_double), value :: tau_fs, bulk_modulus_GPa, max_strain
+     end function
+     integer(c_int) function rxmd_hip_get_barostat(h, p6_GPa, mu, volume, couplings) bind(c, name='rxmd_hip_get_barostat')
+       import :: c_ptr, c_int, c_double, c_long_long
+       type(c_ptr), value :: h
+       real(c_double), intent(out) :: p6_GPa(6), mu(3), volume
+       integer(c_long_long), intent(out) :: couplings
+     end function
   end interface
 
 contains

@@ -126,6 +126,29 @@ int rxmd_hip_thermostat(rxmd_handle h, int mdmode, double treq_K, double vsfact,
  * Pressure as printed: sum(astr[0..2])/3 / MDBOX * 6.94728103 / pstep  [GPa] (main.F90:233,252). */
 int rxmd_hip_get_energy(rxmd_handle h, double *ke, double *qsum, double pe[14], double astr[6]);
 
+/* ---- variable cell: a new lattice for a live engine, Berendsen barostat --------------------- */
+/* Replace the lattice of the WHOLE box (lat[6] as rxmd_config.lattice).  Every resident keeps its normalised coordinates:
+ * r' = H' H^-1 r (PQEq shell displacements d' = H' H^-1 d) on the device; velocities, charges, forces, Lex state unchanged.  The
+ * box-dependent set-up (ghost shell, cell grid, the reference's cell meshes) is derived again and the capacity grows when the new
+ * ghost shell needs more atom slots (rxmd_config.nbuffer = 0).  Collective: every rank passes the same lattice.  RXMD_E_ARG and
+ * the old lattice kept for lengths <= 0, degenerate angles, a local box below the bond cutoff, lattices that differ between ranks.
+ * No counterpart in the reference (its box is fixed after INITSYSTEM). */
+int rxmd_hip_set_lattice(rxmd_handle h, const double lat[6]);
+int rxmd_hip_get_lattice(rxmd_handle h, double lat[6]);      /* the current lattice (after barostat steps too) */
+/* mode 0 off (default), 1 isotropic (P = trace/3, P0 = p0_GPa[0], the three lattice lengths scale together, any cell),
+ * 2 per axis (orthorhombic cells only: lattice length a scales with P_aa and p0_GPa[a]; only axes in the bit mask `axes` move).
+ * Every `every`-th step of rxmd_hip_step, behind its second half-kick:
+ *   mu_a = [1 - (every*dt/tau) (P0_a - P_a) / B]^(1/3), |mu_a - 1| clamped to max_strain, lattice lengths *= mu, angles kept.
+ * P_ab [GPa] = (sum_res m v_a v_b + sum_res+ghost r_a f_b) / V * 6.94728103  -- the sums PRINTE prints (main.F90:225-252, pstep = 1),
+ * of that step only, summed over all ranks; V = volume of the whole box at which the forces were computed (before the remap).
+ * One host wait per coupling (the new lattice); mode 0 adds nothing to a step.  Thermostats combine as a host loop
+ * (rxmd_hip_thermostat, then rxmd_hip_step(h, sstep)).  RXMD_E_ARG: tau_fs or bulk_modulus_GPa <= 0, every < 1, max_strain outside
+ * (0, 0.1], mode 2 on a non-orthorhombic cell.  No counterpart in the reference. */
+int rxmd_hip_set_barostat(rxmd_handle h, int mode, int axes, const double p0_GPa[3], double tau_fs, double bulk_modulus_GPa,
+                          int every, double max_strain);
+/* last coupling: pressure tensor (xx,yy,zz,yz,zx,xy) [GPa], mu[3], volume [A^3] the pressure was computed at, number of couplings so far */
+int rxmd_hip_get_barostat(rxmd_handle h, double p6_GPa[6], double mu[3], double *volume, long long *couplings);
+
 /* ---- the same path behind the reference's own argument shapes ------------------------------- */
 /* Host arrays in the reference layout: atype(NBUFFER) packed type+gid*1e-13, pos/f(NBUFFER,3)
  * column-major REAL coordinates, residents 1..natoms.  These upload, run the device path and

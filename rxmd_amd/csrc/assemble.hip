@@ -447,6 +447,70 @@ void Engine::remove_momentum() {                  // LinearMomentum (main.F90:76
   k_scale_velocities<<<nblk(N, 256), 256, 0, stream>>>(N, sargs, type, vel[0], vel[1], vel[2]);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Berendsen barostat (rxmd_hip_set_barostat; no counterpart in the reference, whose box is fixed after INITSYSTEM).  On a coupling step:
+//   k_bar_head  at the head of the step: the stress accumulators astr (scal[48..53]) copied aside (scal[SCAL_BAR_HEAD..+6), behind the CG snapshot slots: QEq runs between head and sums) -- astr itself is left as
+//               it is, so rxmd_hip_get_energy reads and resets exactly what it does without a barostat
+//   k_bar_sums  behind the second half-kick: the step's own sums = astr - head (virial of this step's FORCE, ENbond's pair correction
+//               included, + m v v of this step), scal[SCAL_BAR_STEP..+6); then summed over the ranks (RCCL in stream order, or the host all-reduce)
+//   k_bar_mu    one thread: P_ab = sums / V * 6.94728103 [GPa] (the factor of PRINTE, main.F90:252) and mu, stored straight into pinned host memory
+// The host waits for mu -- the one host wait of a coupling: the next step's migration, cell binning and torsion images take the box by value --
+// and applies the scaled lattice as rxmd_hip_set_lattice does (Engine::apply_lattice).
+__global__ void k_bar_head(const double *__restrict__ acc6, double *__restrict__ head6) {
+  const int c = threadIdx.x;
+  if (c < 6) head6[c] = acc6[c];
+}
+__global__ void k_bar_sums(const double *__restrict__ acc6, const double *__restrict__ head6, double *__restrict__ step6) {
+  const int c = threadIdx.x;
+  if (c < 6) step6[c] = acc6[c] - head6[c];
+}
+struct BarArgs { int mode, axes; double p0[3], rate, B, max_strain, volume; };   // rate = every * dt / tau
+__global__ void k_bar_mu(const double *__restrict__ step6, BarArgs a, double *out9) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double p[6];
+  for (int c = 0; c < 6; ++c) p[c] = step6[c] / a.volume * 6.94728103;
+  for (int k = 0; k < 3; ++k) {
+    double m = 1.0;
+    if (a.mode == 1) m = cbrt(1.0 - a.rate * (a.p0[0] - (p[0] + p[1] + p[2]) / 3.0) / a.B);
+    else if ((a.axes >> k) & 1) m = cbrt(1.0 - a.rate * (a.p0[k] - p[k]) / a.B);
+    out9[6 + k] = fmin(fmax(m, 1.0 - a.max_strain), 1.0 + a.max_strain);
+  }
+  for (int c = 0; c < 6; ++c) out9[c] = p[c];
+}
+
+void Engine::barostat_couple() {
+  double *head6 = scal + SCAL_BAR_HEAD, *step6 = scal + SCAL_BAR_STEP;
+  k_bar_sums<<<1, 64, 0, stream>>>(scal + 48, head6, step6);
+  if (nprocs > 1) {
+    const bool kt = kt_begin(&st.ms_allreduce, nullptr, &st.allreduce_calls);
+    struct End { Engine *e; bool kt; ~End() { e->kt_end(kt); } } end_{this, kt};
+    if (nccl) rccl_allreduce_dev(step6, 6);                            // in stream order
+    else {
+      if (!has_comm || !comm.allreduce_sum) throw EngineError(RXMD_E_COMM, "vprocs > 1 needs a transport: call rxmd_hip_set_comm or rxmd_hip_comm_init_rccl first");
+      RX_HIP(hipMemcpyAsync(h_scal + 304, step6, sizeof(double) * 6, hipMemcpyDeviceToHost, stream));
+      sync_stream();
+      if (comm.allreduce_sum(comm.ctx, h_scal + 304, 6)) throw EngineError(RXMD_E_COMM, "allreduce callback failed");
+      RX_HIP(hipMemcpyAsync(step6, h_scal + 304, sizeof(double) * 6, hipMemcpyHostToDevice, stream));
+    }
+  }
+  BarArgs a{};
+  a.mode = bar_mode; a.axes = bar_axes;
+  for (int k = 0; k < 3; ++k) a.p0[k] = bar_p0[k];
+  a.rate = bar_every * cfg.dt_fs / bar_tau; a.B = bar_B; a.max_strain = bar_max; a.volume = box.volume;   // the volume the forces of this step were computed at
+  double *out9 = h_scal + 288;                                         // [288, 297) of the pinned block: p6, mu
+  k_bar_mu<<<1, 64, 0, stream>>>(step6, a, out9);
+  sync_stream();
+  for (int c = 0; c < 6; ++c) bar_p6[c] = out9[c];
+  for (int k = 0; k < 3; ++k) bar_mu[k] = out9[6 + k];
+  bar_vol = box.volume;
+  ++bar_couplings;
+  double lat[6];
+  for (int k = 0; k < 3; ++k) lat[k] = box.lat[k] * bar_mu[k];      // lengths scaled, angles kept
+  for (int k = 3; k < 6; ++k) lat[k] = box.lat[k];
+  check_lattice(lat);
+  apply_lattice(lat);
+}
+
 void Engine::step(int nsteps) {
   if (!atoms_set) throw EngineError(RXMD_E_STATE, "atoms were never set");
   // The event pairs of the per-kernel timers (rxmd_stats.ms_k_*, ms_bo, ms_nonbond, ...) cost the stream ~5 us per event, ~12 pairs per step.  A call of 8
@@ -456,6 +520,8 @@ void Engine::step(int nsteps) {
   struct Restore { Engine *e; ~Restore() { e->kt_every = 1; e->kt_phase = 0; } } restore_{this};
   for (int s = 0; s < nsteps; ++s) {
     kt_phase = s;
+    const bool couple = bar_mode != 0 && (step_count + 1) % bar_every == 0;   // barostat: every `every`-th step (mode 0: nothing new is launched)
+    if (couple) k_bar_head<<<1, 64, 0, stream>>>(scal + 48, scal + SCAL_BAR_HEAD);
     if (cfg.efield_dir != 0) {             // always correct the linear momentum when an electric field is applied (main.F90:70-71)
       k_kick<<<nblk(N, 256), 256, 0, stream>>>(N, dff, dt, Lex_w2, type, vel[0], vel[1], vel[2], frc[0], frc[1], frc[2], q, qsfp, qsfv);
       k_lex_drift<<<nblk(N, 256), 256, 0, stream>>>(N, dt, qsfp, qsfv);
@@ -470,6 +536,7 @@ void Engine::step(int nsteps) {
     accumulate_stress(true);                                             // main.F90:86-94
     k_kick<<<nblk(N, 256), 256, 0, stream>>>(N, dff, dt, Lex_w2, type, vel[0], vel[1], vel[2], frc[0], frc[1], frc[2], q, qsfp, qsfv);
     ++step_count;
+    if (couple) barostat_couple();
   }
   finish_force();
   sync_stream();

@@ -249,6 +249,27 @@ int rxmd_hip_get_energy(rxmd_handle h, double *ke, double *qsum, double pe[14], 
   });
 }
 
+// ---- variable cell (no counterpart in the reference: its box is fixed after INITSYSTEM) ----
+int rxmd_hip_set_lattice(rxmd_handle h, const double lat[6]) {
+  if (!lat) return RXMD_E_ARG;
+  return guarded(h, [&](Engine &e) { e.set_lattice(lat, true); });
+}
+int rxmd_hip_get_lattice(rxmd_handle h, double lat[6]) {
+  if (!lat) return RXMD_E_ARG;
+  return guarded(h, [&](Engine &e) { std::memcpy(lat, e.box.lat, sizeof(double) * 6); });
+}
+int rxmd_hip_set_barostat(rxmd_handle h, int mode, int axes, const double p0_GPa[3], double tau_fs, double bulk_modulus_GPa, int every, double max_strain) {
+  return guarded(h, [&](Engine &e) { e.set_barostat(mode, axes, p0_GPa, tau_fs, bulk_modulus_GPa, every, max_strain); });
+}
+int rxmd_hip_get_barostat(rxmd_handle h, double p6_GPa[6], double mu[3], double *volume, long long *couplings) {
+  return guarded(h, [&](Engine &e) {
+    if (p6_GPa) std::memcpy(p6_GPa, e.bar_p6, sizeof(double) * 6);
+    if (mu) std::memcpy(mu, e.bar_mu, sizeof(double) * 3);
+    if (volume) *volume = e.bar_vol;
+    if (couplings) *couplings = e.bar_couplings;
+  });
+}
+
 // ---- the reference's own argument shapes (QEq(atype,pos,q) qeq.F90:2 ; FORCE(atype,pos,f,q) pot.F90:2) ----
 static void upload_reference_arrays(Engine &e, int nbuffer, int natoms, const double *atype, const double *pos, const double *q) {
   if (natoms < 0 || (natoms == 0 && e.nprocs == 1) || nbuffer < natoms) throw EngineError(RXMD_E_ARG, "bad natoms/nbuffer");

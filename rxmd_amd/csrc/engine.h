@@ -105,6 +105,11 @@ struct RefMesh {
 
 constexpr int WAVE = 64;
 
+// the device scalar block `scal` (double): [0, S_COUNT) CG scalars (spmv_kernels.h), [32, 48) energies, [48, 54) the stress accumulators astr,
+// [56, 62) PRINTE's sums, [64, 72) staging of the host all-reduce, [128, 192) the two CG snapshot slots (S_SNAP), and the barostat's own
+// 6-vectors behind them: the step-head copy of astr and the step's sums
+constexpr int SCAL_BAR_HEAD = 192, SCAL_BAR_STEP = 200, SCAL_N = 208;
+
 // XCD-aware workgroup order: the dispatcher deals consecutive workgroup ids round-robin to the 8 XCDs (each with its own L2),
 // so without a remap every L2 sees rows from all over the box and re-fetches the whole gather vector.  With it the
 // workgroups that share an XCD own one contiguous eighth of the rows = one compact region of space (bijective for any grid).
@@ -290,6 +295,28 @@ struct Engine {
   void thermostat(int mdmode, double treq_K, double vsfact, double gke);   // velocity scaling of the MD loop head (assemble.hip)
   int minimise(double ftol, int max_loops, double *pe_final, long long *evaluations);   // mdmode 10: the reference's conjugate-gradient minimiser (minimise.hip)
 
+  // ---- variable cell (engine.hip: set_lattice; assemble.hip: the barostat of step()) ----
+  // set_lattice: the residents keep their normalised coordinates (k_affine_remap), the box-dependent half of the set-up is derived
+  // again (derive_box_geometry), buffers sized by the grid follow it, and the per-atom capacity grows when the new ghost shell needs it
+  void set_lattice(const double lat[6], bool check_ranks);
+  void apply_lattice(const double lat[6]);     // no validation: the caller checked (set_lattice) or computed the lattice from all-reduced sums (barostat)
+  void check_lattice(const double lat[6]) const;   // RXMD_E_ARG for a lattice that spans no box or a local box below the bond cutoff
+  struct BoxGeom { int cc[3]; double shell[3]; Grid grid; RefMesh rmesh; };
+  BoxGeom geometry_for(const Box &b) const;    // cc, shell, grid, rmesh of box b (the part of setup_after_atoms that depends on the lattice)
+  void derive_box_geometry();                  // the same for `box`, into the members
+  long long capacity_want(const double shell_n[3]) const;   // the NB set-up would choose for a ghost shell shell_n (rxmd_config.nbuffer = 0)
+  void grow_capacity(int new_nb);              // every per-atom buffer re-allocated at new_nb; the residents' state and the device scalars kept
+  void alloc_window_groups(size_t nb, size_t ng);   // ng window groups (win_groups_bound(rows10) + 1 of a grid) + rpos / g_rrow
+  size_t cellstart_cap = 0, win_ng_cap = 0;    // what is allocated: grid.nfine + 2 ; win_groups_bound(rows10) + 1 of the grid they were sized for
+  long long nsize_setup = 0;                   // the per-rank atom count set-up sized the engine for
+  // Berendsen barostat (rxmd_hip_set_barostat): mode 0 off, 1 isotropic, 2 per axis; coupled behind the second half-kick of every `every`-th step
+  int bar_mode = 0, bar_axes = 7, bar_every = 1;
+  double bar_p0[3] = {0, 0, 0}, bar_tau = 0, bar_B = 0, bar_max = 0;
+  double bar_p6[6] = {0, 0, 0, 0, 0, 0}, bar_mu[3] = {1, 1, 1}, bar_vol = 0;   // last coupling: pressure tensor [GPa], factors, the volume the forces were computed at
+  long long bar_couplings = 0;
+  void set_barostat(int mode, int axes, const double p0[3], double tau_fs, double bulk_GPa, int every, double max_strain);
+  void barostat_couple();
+
   // pieces (each in its own .hip)
   void setup_after_atoms(const std::vector<long long> &natoms_per_type_global);
   void upload_ff();
@@ -325,7 +352,8 @@ struct Engine {
   int *r_type = nullptr, *r_n10 = nullptr, *r_xpos = nullptr, *rpos = nullptr, *g_rrow = nullptr;   // per row: type (0 = not a row), row length, cell-sorted position; per atom: its row; per ghost: the row of its owner
   int win_groups = 0, win_maxunits = 0;
   // upper bound of the window groups of n rows: a group holds WIN_ROWS rows of ONE cell column (x, y) of the grid, every column may end in a short group
-  size_t win_groups_bound(long long n) const { return static_cast<size_t>(n) / WIN_ROWS + static_cast<size_t>(grid.n[0]) * grid.n[1] + 1; }
+  size_t win_groups_bound(long long n) const { return win_groups_bound_for(grid, n); }
+  static size_t win_groups_bound_for(const Grid &g, long long n) { return static_cast<size_t>(n) / WIN_ROWS + static_cast<size_t>(g.n[0]) * g.n[1] + 1; }
   double qeq_iters_smooth = -1.0;               // running mean of the CG iterations per QEq call (the exit test of qeq.F90:114-115 lets single calls stop after two or three)
   bool win_valid = false, win_used = false;    // win_used: the last matrix pass was a window pass
   void halo_refresh(double2 *v2, double *v1);       // QCOPY1/QCOPY2: ghosts <- owners (self exchange, resolved roots)

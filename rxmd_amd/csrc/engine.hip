@@ -74,6 +74,17 @@ static void make_box(Box &b, const double lat[6], const int vprocs[3], const int
   for (int a = 0; a < 3; ++a) { b.lbox[a] = 1.0 / vprocs[a]; b.obox[a] = b.lbox[a] * vID[a]; }
 }
 
+// a box the H matrix of GetBoxParams (init.F90:610-633) can describe: positive edges, angles inside (0,180), nonzero volume (NaN fails every test)
+static bool lattice_spans_box(const double *L) {
+  const double d2r = std::atan(1.0) / 45.0;
+  const double ca = std::cos(L[3] * d2r), cb = std::cos(L[4] * d2r), cg = std::cos(L[5] * d2r);
+  const double v2 = 1.0 - ca * ca - cb * cb - cg * cg + 2.0 * ca * cb * cg;
+  bool ok = L[0] > 0.0 && L[1] > 0.0 && L[2] > 0.0 && v2 > 1e-12;
+  for (int a = 3; a < 6; ++a) ok = ok && L[a] > 0.0 && L[a] < 180.0;
+  return ok;
+}
+static bool lattice_orthorhombic(const double *L) { return std::fabs(L[3] - 90.0) < 1e-9 && std::fabs(L[4] - 90.0) < 1e-9 && std::fabs(L[5] - 90.0) < 1e-9; }   // (the test of grid.ortho)
+
 Engine::Engine(const rxmd_config &c) : cfg(c) {
   if (!c.ffield_path) throw EngineError(RXMD_E_ARG, "ffield_path is NULL");
   ffield_path = c.ffield_path;
@@ -81,14 +92,7 @@ Engine::Engine(const rxmd_config &c) : cfg(c) {
   for (int a = 0; a < 3; ++a) if (cfg.vprocs[a] < 1) throw EngineError(RXMD_E_ARG, "vprocs must be >= 1");
   nprocs = cfg.vprocs[0] * cfg.vprocs[1] * cfg.vprocs[2];
   if (cfg.myid < 0 || cfg.myid >= nprocs) throw EngineError(RXMD_E_ARG, "myid outside the vprocs grid");
-  {   // a box the H matrix of GetBoxParams (init.F90:610-633) cannot describe: non-positive edge, angle outside (0,180), zero volume
-    const double *L = cfg.lattice, d2r = std::atan(1.0) / 45.0;
-    const double ca = std::cos(L[3] * d2r), cb = std::cos(L[4] * d2r), cg = std::cos(L[5] * d2r);
-    const double v2 = 1.0 - ca * ca - cb * cb - cg * cg + 2.0 * ca * cb * cg;
-    bool ok = L[0] > 0.0 && L[1] > 0.0 && L[2] > 0.0 && v2 > 1e-12;
-    for (int a = 3; a < 6; ++a) ok = ok && L[a] > 0.0 && L[a] < 180.0;
-    if (!ok) throw EngineError(RXMD_E_ARG, "lattice does not span a box (edges must be positive, angles inside (0,180) and not coplanar)");
-  }
+  if (!lattice_spans_box(cfg.lattice)) throw EngineError(RXMD_E_ARG, "lattice does not span a box (edges must be positive, angles inside (0,180) and not coplanar)");
   try { ff.parse(ffield_path, cfg.lg != 0); } catch (const std::exception &e) { throw EngineError(RXMD_E_FFIELD, e.what()); }
   // rank grid, reference src/init.F90:74-100
   vID[0] = cfg.myid % cfg.vprocs[0]; vID[1] = (cfg.myid / cfg.vprocs[0]) % cfg.vprocs[1]; vID[2] = cfg.myid / (cfg.vprocs[0] * cfg.vprocs[1]);
@@ -233,6 +237,16 @@ void Engine::setup_after_atoms(const std::vector<long long> &npt) {
   ff.compute_cutoffs(npt);
   ff.build_tables();
   if (ff.pqeq) ff.build_pqeq_tables();
+  derive_box_geometry();
+  tables_ready = true;
+}
+
+// the half of the set-up that depends on the lattice (UpdateBoxParams, init.F90:641-667, and the engine's own grid) for box `box`: set-up and
+// set_lattice (which computes it for the new box before it changes anything)
+Engine::BoxGeom Engine::geometry_for(const Box &box) const {
+  BoxGeom g;
+  int *cc = g.cc; double *shell = g.shell; Grid &grid = g.grid; RefMesh &rmesh = g.rmesh;
+  grid = this->grid;                               // (fields the lattice does not decide, such as the probe switch, stay)
   const double lreal[3] = {box.lat[0] / cfg.vprocs[0], box.lat[1] / cfg.vprocs[1], box.lat[2] / cfg.vprocs[2]};
   for (int a = 0; a < 3; ++a) {
     cc[a] = static_cast<int>(lreal[a] / ff.maxrc);            // UpdateBoxParams, init.F90:656
@@ -272,7 +286,12 @@ void Engine::setup_after_atoms(const std::vector<long long> &npt) {
   while (grid.fz > 1 && static_cast<long long>(grid.ncell) * grid.fz > (1LL << 28)) grid.fz >>= 1;
   grid.nzf = grid.n[2] * grid.fz;
   grid.nfine = grid.n[0] * grid.n[1] * grid.nzf;
-  tables_ready = true;
+  return g;
+}
+void Engine::derive_box_geometry() {
+  const BoxGeom g = geometry_for(box);
+  for (int a = 0; a < 3; ++a) { cc[a] = g.cc[a]; shell[a] = g.shell[a]; }
+  grid = g.grid; rmesh = g.rmesh;
 }
 
 void Engine::upload_ff() {
@@ -380,7 +399,8 @@ void Engine::alloc_device() {
   dmalloc(qst, nb); dmalloc(hst, nb); dmalloc(gst, nb); dmalloc(hst2, nb); dzalloc(tickets, 16);
   { dmalloc(sall, static_cast<size_t>(rows10)); dmalloc(sgh, static_cast<size_t>(rows10)); dmalloc(wall, static_cast<size_t>(rows10)); dmalloc(wgh, static_cast<size_t>(rows10)); }
   dmalloc(gsrc, nb); dmalloc(groot, nb); dmalloc(gowner, nb); dmalloc(dh_ghost, nb); dmalloc(dh_keys, nb); dmalloc(dh_keys2, nb); dmalloc(dh_vals, nb); dmalloc(dh_off, 1100); dmalloc(sendidx, nb); dmalloc(rootperm, nb); dmalloc(invpos, nb); dmalloc(xs, nb); for (int a = 0; a < 3; ++a) { dmalloc(fnb[a], nb); dmalloc(fsort[a], nb); }
-  dmalloc(cellid, nb); dmalloc(cellid_sorted, nb); dmalloc(perm, nb); dmalloc(perm_in, nb); dmalloc(cellstart, static_cast<size_t>(grid.nfine) + 2);
+  cellstart_cap = static_cast<size_t>(grid.nfine) + 2;
+  dmalloc(cellid, nb); dmalloc(cellid_sorted, nb); dmalloc(perm, nb); dmalloc(perm_in, nb); dmalloc(cellstart, cellstart_cap);
   dmalloc(sorted_xyzi, nb); dmalloc(sorted_type, nb); dmalloc(flags, nb + 1); dmalloc(scanout, nb + 1); dmalloc(flags2, nb + 1); dmalloc(scanout2, nb + 1);
   dmalloc(nbr_sm, ns); dmalloc(nbrcnt, nb + 1); dmalloc(boff, nb + 2);
   {   // 5.3 bonds per RDX atom, ~16 in SiC: 12 per atom slot to start with, grown when a build needs more (build_ghosts_and_lists).
@@ -394,12 +414,10 @@ void Engine::alloc_device() {
   dmalloc(nb10, static_cast<size_t>(rows10) * S10);
   dmalloc(rows_int, static_cast<size_t>(rows10)); dmalloc(rows_bnd, static_cast<size_t>(rows10));
   dmalloc(hess, static_cast<size_t>(rows10) * S10); dmalloc(n10, static_cast<size_t>(rows10));
-  { const size_t ng = win_groups_bound(rows10) + 1;       // groups never straddle a cell column of the grid: up to one short group per column
-    for (double2 **pp : {&r_qst, &r_hst, &r_hst2, &r_gst, &r_sall, &r_sgh, &r_wall, &r_wgh}) dmalloc(*pp, ng * WIN_ROWS);
-    dmalloc(r_type, ng * WIN_ROWS); dmalloc(r_n10, ng * WIN_ROWS); dmalloc(r_xpos, ng * WIN_ROWS); dmalloc(rpos, nb); dmalloc(g_rrow, nb);
-    dmalloc(rows_sorted, ng * WIN_ROWS); dmalloc(rowcols, ng * WIN_ROWS * 64); dmalloc(grp_base, ng * 32); dmalloc(win_flag, ng + 1); dmalloc(win_k, ng * WIN_MAXUNITS); dmalloc(win_cnt, ng); dmalloc(win_gint, ng); dmalloc(win_gbnd, ng); dmalloc(sl10, static_cast<size_t>(rows10) * S10); }
+  alloc_window_groups(nb, win_groups_bound(rows10) + 1);
+  dmalloc(sl10, static_cast<size_t>(rows10) * S10);
   partials_cap = std::max<size_t>(size_t(1) << 16, 4 * static_cast<size_t>(rows10) + 16384);   // up to one workgroup (4 partial sums) per row
-  dmalloc(partials, partials_cap + 1024); dzalloc(scal, 192);   // + the 128 x 4 first-level sums of k_reduce_fused, behind the per-workgroup partials at a fixed offset
+  dmalloc(partials, partials_cap + 1024); dzalloc(scal, SCAL_N);   // + the 128 x 4 first-level sums of k_reduce_fused, behind the per-workgroup partials at a fixed offset
   RX_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_scal), 320 * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));   // coherent: the update kernel's tail stores the CG snapshot into it and the host polls it      // [0,64): as before; [64,192): the two slots of the run-ahead CG loop (qeq.hip); [192,288): the per-type sums of a host transport
   dzalloc(tsum, 128); { double *sa_ = nullptr; dzalloc(sa_, 32); sargs = reinterpret_cast<ScaleArgs *>(sa_); }
   dzalloc(d_err, 16);
@@ -411,6 +429,14 @@ void Engine::alloc_device() {
   hipcub::DeviceRadixSort::SortPairs(nullptr, b2, cellid, cellid_sorted, perm_in, perm, NB, 0, 32, stream);
   cubtmp_bytes = std::max(b1, b2) + 256;
   RX_HIP(hipMalloc(&cubtmp, cubtmp_bytes));
+}
+
+// groups never straddle a cell column of the grid: up to one short group per column (win_groups_bound)
+void Engine::alloc_window_groups(size_t nb, size_t ng) {
+  win_ng_cap = ng;
+  for (double2 **pp : {&r_qst, &r_hst, &r_hst2, &r_gst, &r_sall, &r_sgh, &r_wall, &r_wgh}) dmalloc(*pp, ng * WIN_ROWS);
+  dmalloc(r_type, ng * WIN_ROWS); dmalloc(r_n10, ng * WIN_ROWS); dmalloc(r_xpos, ng * WIN_ROWS); dmalloc(rpos, nb); dmalloc(g_rrow, nb);
+  dmalloc(rows_sorted, ng * WIN_ROWS); dmalloc(rowcols, ng * WIN_ROWS * 64); dmalloc(grp_base, ng * 32); dmalloc(win_flag, ng + 1); dmalloc(win_k, ng * WIN_MAXUNITS); dmalloc(win_cnt, ng); dmalloc(win_gint, ng); dmalloc(win_gbnd, ng);
 }
 
 void Engine::alloc_bond_tables(size_t cap) {
@@ -490,10 +516,8 @@ void Engine::set_atoms_rxff(int natoms, const double *rec) {
     long long ntot = 0;
     for (int t = 1; t <= ff.nso; ++t) ntot += npt[t];
     const long long nsize = std::max<long long>(natoms, ntot / nprocs);
-    double fac = 1.0;
-    for (int a = 0; a < 3; ++a) fac *= 1.0 + 2.0 * std::min(shell[a] / box.lbox[a], 1.0);
-    const long long want = static_cast<long long>(nsize * fac * 1.12) + 4096;
-    NB = cfg.nbuffer > 0 ? cfg.nbuffer : static_cast<int>(std::min<long long>(want, 2000000000LL));
+    nsize_setup = nsize;
+    NB = cfg.nbuffer > 0 ? cfg.nbuffer : static_cast<int>(capacity_want(shell));
     if (NB <= natoms) throw EngineError(RXMD_E_NBUFFER, "nbuffer smaller than natoms");
     const double vloc = box.volume / nprocs;
     const double est10 = nsize / vloc * (4.0 / 3.0) * 3.14159265358979 * ff.rctap * ff.rctap2;
@@ -1574,7 +1598,7 @@ void Engine::poison_step_scratch() {
   fill(q, sizeof(double) * N, sizeof(double) * ng); fill(type, sizeof(int) * N, sizeof(int) * ng); fill(gid, sizeof(long long) * N, sizeof(long long) * ng);
   fill(gsrc, 0, sizeof(int) * nb); fill(groot, 0, sizeof(int) * nb); fill(rootperm, 0, sizeof(int) * nb); fill(invpos, 0, sizeof(int) * nb); fill(xs, 0, sizeof(double2) * nb);
   fill(cellid, 0, sizeof(int) * nb); fill(cellid_sorted, 0, sizeof(int) * nb); fill(perm, 0, sizeof(int) * nb); fill(perm_in, 0, sizeof(int) * nb);
-  fill(cellstart, 0, sizeof(int) * (static_cast<size_t>(grid.nfine) + 2)); fill(sorted_xyzi, 0, sizeof(double4) * nb); fill(sorted_type, 0, nb);
+  fill(cellstart, 0, sizeof(int) * cellstart_cap); fill(sorted_xyzi, 0, sizeof(double4) * nb); fill(sorted_type, 0, nb);
   if (ff.pqeq) { fill(sorted_shl, 0, sizeof(double4) * nb); fill(hsc, 0, sizeof(double) * nl); fill(pqrow, 0, sizeof(double4) * rows10); for (int a = 0; a < 3; ++a) fill(shl[a], sizeof(double) * N, sizeof(double) * ng); }
   fill(nbr_sm, 0, sizeof(int) * ns); fill(nbrcnt, 0, sizeof(int) * (nb + 1)); fill(boff, 0, sizeof(int) * (nb + 2));
   fill(nbr, 0, sizeof(int) * bcap); fill(brev, 0, sizeof(int) * bcap); fill(bown, 0, sizeof(int) * bcap); fill(btype, 0, bcap);
@@ -1583,7 +1607,7 @@ void Engine::poison_step_scratch() {
   for (double *t : {deltap, delta, nlp, dDlp, deltalp, cds, cd, cc_}) fill(t, 0, sizeof(double) * nb);
   fill(nb10, 0, sizeof(int) * nl); fill(hess, 0, sizeof(double) * nl); fill(sl10, 0, sizeof(unsigned short) * nl); fill(n10, 0, sizeof(int) * rows10);
   fill(rows_int, 0, sizeof(int) * rows10); fill(rows_bnd, 0, sizeof(int) * rows10);
-  { const size_t ngr = win_groups_bound(rows10) + 1;
+  { const size_t ngr = win_ng_cap;                 // (the sizes allocated: set_lattice re-allocates these when the grid outgrows them)
     fill(rows_sorted, 0, sizeof(int) * ngr * WIN_ROWS); fill(rowcols, 0, sizeof(int) * ngr * WIN_ROWS * 64); fill(grp_base, 0, sizeof(int) * ngr * 32); fill(win_flag, 0, sizeof(int) * (ngr + 1)); fill(win_k, 0, sizeof(int) * ngr * WIN_MAXUNITS); fill(win_cnt, 0, sizeof(int) * ngr);
     fill(win_gint, 0, sizeof(int) * ngr); fill(win_gbnd, 0, sizeof(int) * ngr); }
   fill(sall, 0, sizeof(double2) * rows10); fill(sgh, 0, sizeof(double2) * rows10); fill(wall, 0, sizeof(double2) * rows10); fill(wgh, 0, sizeof(double2) * rows10);
@@ -1645,6 +1669,162 @@ void Engine::build_ghosts_and_lists(bool qeq_prepass) {
   collect_timers();
   outer_end(t_lists);
   lists_valid = true;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Variable cell: a new lattice for a live engine (rxmd_hip_set_lattice, and the barostat of step()).  No counterpart in the reference:
+// its box is fixed after INITSYSTEM.
+//
+// r' = M r with M = H' H^-1 (row-major): every resident keeps its normalised coordinates; the PQEq shell displacements follow the same map
+struct Mat3 { double m[9]; };
+__global__ void k_affine_remap(int n, Mat3 M, double *__restrict__ x, double *__restrict__ y, double *__restrict__ z,
+                               double *__restrict__ dx, double *__restrict__ dy, double *__restrict__ dz) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double r0 = x[i], r1 = y[i], r2 = z[i];
+  x[i] = M.m[0] * r0 + M.m[1] * r1 + M.m[2] * r2;
+  y[i] = M.m[3] * r0 + M.m[4] * r1 + M.m[5] * r2;
+  z[i] = M.m[6] * r0 + M.m[7] * r1 + M.m[8] * r2;
+  if (dx) {
+    const double d0 = dx[i], d1 = dy[i], d2 = dz[i];
+    dx[i] = M.m[0] * d0 + M.m[1] * d1 + M.m[2] * d2;
+    dy[i] = M.m[3] * d0 + M.m[4] * d1 + M.m[5] * d2;
+    dz[i] = M.m[6] * d0 + M.m[7] * d1 + M.m[8] * d2;
+  }
+}
+
+void Engine::check_lattice(const double lat[6]) const {
+  if (!lattice_spans_box(lat)) throw EngineError(RXMD_E_ARG, "lattice does not span a box (edges must be positive, angles inside (0,180) and not coplanar)");
+  if (tables_ready)                                          // (before the atoms are set there is no cutoff yet: set-up checks it)
+    for (int a = 0; a < 3; ++a)
+      if (static_cast<int>(lat[a] / cfg.vprocs[a] / ff.maxrc) < 1) throw EngineError(RXMD_E_ARG, "local box smaller than the bond cutoff");
+  if (bar_mode == 2 && !lattice_orthorhombic(lat)) throw EngineError(RXMD_E_ARG, "the per-axis barostat (mode 2) is on: the lattice must stay orthorhombic");
+}
+
+// the NB set-up chooses (set_atoms_rxff): the residents it was sized for times the volume of the box with its ghost shell, + 12 % + 4096
+long long Engine::capacity_want(const double shell_n[3]) const {
+  const long long nsize = std::max<long long>(nsize_setup, N);
+  double fac = 1.0;
+  for (int a = 0; a < 3; ++a) fac *= 1.0 + 2.0 * std::min(shell_n[a] / box.lbox[a], 1.0);
+  const long long want = static_cast<long long>(nsize * fac * 1.12) + 4096;
+  return std::min<long long>(want, 2000000000LL);
+}
+
+// Collective with several ranks: one all-reduce carries rank 0's six values (every other rank adds zeros, so the sum is rank 0's lattice
+// bit for bit) and the count of ranks whose lattice failed its local checks; every rank compares its own lattice with rank 0's EXACTLY, and
+// a second all-reduce of the mismatches makes the decision the same everywhere.  Everything is checked before any state changes.
+void Engine::set_lattice(const double lat[6], bool check_ranks) {
+  bool local_ok = true;
+  std::string why;
+  try { check_lattice(lat); } catch (const EngineError &er) { if (nprocs == 1 || !check_ranks) throw; local_ok = false; why = er.msg; }
+  if (check_ranks && nprocs > 1) {
+    double s[7];
+    for (int a = 0; a < 6; ++a) s[a] = cfg.myid == 0 ? lat[a] : 0.0;
+    s[6] = local_ok ? 0.0 : 1.0;
+    allreduce_host(s, 7);
+    double bad = 0.0;
+    for (int a = 0; a < 6; ++a) if (!(s[a] == lat[a])) bad = 1.0;        // (exact; a NaN anywhere is a mismatch)
+    allreduce_host(&bad, 1);
+    if (!local_ok) throw EngineError(RXMD_E_ARG, why);
+    if (s[6] != 0.0) throw EngineError(RXMD_E_ARG, "set_lattice is collective: another rank's lattice failed its checks");
+    if (bad != 0.0) throw EngineError(RXMD_E_ARG, "set_lattice is collective: the ranks passed different lattices");
+  }
+  apply_lattice(lat);
+}
+
+// Everything the new lattice needs is computed and allocated while the engine is still at the old one (the geometry of the new box, the
+// buffers sized by its grid, the capacity its ghost shell needs); only then are the residents remapped and the box replaced.
+void Engine::apply_lattice(const double lat[6]) {
+  if (force_pending) finish_force();               // the energies of the last FORCE reach the host before any buffer can move
+  Box nbx{};
+  make_box(nbx, lat, cfg.vprocs, vID);
+  BoxGeom g{};
+  if (tables_ready) {
+    g = geometry_for(nbx);
+    const long long want = cfg.nbuffer <= 0 ? capacity_want(g.shell) : NB;
+    if (want >= (1LL << NB10_IDX_BITS)) throw EngineError(RXMD_E_NBUFFER, "the new lattice needs more than 2^26 atoms+ghosts per GPU (the packed 10 A list entry)");
+    // a wider normalised ghost shell (compression lowered cc) needs more atom slots than set-up allocated: grown at the OLD lattice
+    if (want > NB) grow_capacity(static_cast<int>(want));
+    // buffers sized by the grid: cellstart (cells x z-slices) and the window groups (one short group per grid column at most)
+    const size_t need_cs = static_cast<size_t>(g.grid.nfine) + 2, need_ng = win_groups_bound_for(g.grid, rows10) + 1;
+    if (need_cs > cellstart_cap || need_ng > win_ng_cap) sync_stream();
+    if (need_cs > cellstart_cap) { dfree(cellstart); dmalloc(cellstart, need_cs); cellstart_cap = need_cs; }
+    if (need_ng > win_ng_cap) {
+      for (double2 **pp : {&r_qst, &r_hst, &r_hst2, &r_gst, &r_sall, &r_sgh, &r_wall, &r_wgh}) dfree(*pp);
+      dfree(r_type); dfree(r_n10); dfree(r_xpos); dfree(rpos); dfree(g_rrow);
+      dfree(rows_sorted); dfree(rowcols); dfree(grp_base); dfree(win_flag); dfree(win_k); dfree(win_cnt); dfree(win_gint); dfree(win_gbnd);
+      alloc_window_groups(static_cast<size_t>(NB), need_ng);
+    }
+  }
+  if (atoms_set && N > 0) {
+    Mat3 M;
+    for (int a = 0; a < 3; ++a)
+      for (int c = 0; c < 3; ++c) M.m[3 * a + c] = nbx.H[a][0] * box.Hi[0][c] + nbx.H[a][1] * box.Hi[1][c] + nbx.H[a][2] * box.Hi[2][c];
+    k_affine_remap<<<nblk(N, 256), 256, 0, stream>>>(N, M, pos[0], pos[1], pos[2], ff.pqeq ? shl[0] : nullptr, ff.pqeq ? shl[1] : nullptr, ff.pqeq ? shl[2] : nullptr);
+    RX_HIP(hipGetLastError());
+  }
+  box = nbx;
+  for (int a = 0; a < 6; ++a) cfg.lattice[a] = lat[a];
+  if (tables_ready) {
+    for (int a = 0; a < 3; ++a) { cc[a] = g.cc[a]; shell[a] = g.shell[a]; }
+    grid = g.grid; rmesh = g.rmesh;
+    st.nbuffer = NB;
+    for (int a = 0; a < 3; ++a) { st.cells10[a] = grid.n[a]; st.cells3[a] = cc[a]; }
+  }
+  lists_valid = false; ghosts_valid = false; win_valid = false;
+  last_atype.clear(); for (auto &v : last_pos) v.clear();   // the next array-shaped QEq / FORCE call uploads again
+}
+
+// Growth: the slow exact path.  The residents' state and the device scalars go through the host, every buffer is allocated again at the new
+// capacity as set-up allocates it, and the state comes back.  Re-allocated pinned memory is zeroed: a stale sequence word in h_scal / h_pub
+// could otherwise satisfy a later poll.
+void Engine::grow_capacity(int new_nb) {
+  if (new_nb >= (1 << NB10_IDX_BITS)) throw EngineError(RXMD_E_NBUFFER, "more than 2^26 atoms+ghosts per GPU do not fit the packed 10 A list entry");
+  RX_HIP(hipDeviceSynchronize());                  // (every stream of the engine: the bonded chain and the halo stream included)
+  const size_t n = static_cast<size_t>(N);
+  auto dbl_arrays = [&]() {
+    std::vector<double *> v = {pos[0], pos[1], pos[2], vel[0], vel[1], vel[2], frc[0], frc[1], frc[2], q, qsfp, qsfv};
+    if (ff.pqeq) for (int a = 0; a < 3; ++a) v.push_back(shl[a]);
+    return v;
+  };
+  auto vec_arrays = [&]() { return std::vector<double2 *>{qst, hst, gst}; };
+  std::vector<std::vector<double>> hd;
+  for (double *p : dbl_arrays()) { hd.emplace_back(n); if (n) RX_HIP(hipMemcpy(hd.back().data(), p, sizeof(double) * n, hipMemcpyDeviceToHost)); }
+  std::vector<std::vector<double2>> hv;
+  for (double2 *p : vec_arrays()) { hv.emplace_back(n); if (n) RX_HIP(hipMemcpy(hv.back().data(), p, sizeof(double2) * n, hipMemcpyDeviceToHost)); }
+  std::vector<int> ht(n); std::vector<long long> hg(n); std::vector<double> hs(SCAL_N);
+  if (n) { RX_HIP(hipMemcpy(ht.data(), type, sizeof(int) * n, hipMemcpyDeviceToHost)); RX_HIP(hipMemcpy(hg.data(), gid, sizeof(long long) * n, hipMemcpyDeviceToHost)); }
+  RX_HIP(hipMemcpy(hs.data(), scal, sizeof(double) * SCAL_N, hipMemcpyDeviceToHost));   // CG state, energies, stress accumulators
+  free_device();
+  if (xbuf_owned) xbuf_doubles = 0;                // (host-supplied exchange buffers are the host's and stay)
+  dh_serve_cap = 0; dh_ready = false; rows_live = false; win_valid = false;
+  NB = new_nb;
+  alloc_device();
+  upload_ff();
+  std::memset(h_scal, 0, 320 * sizeof(double));
+  std::memset(h_err, 0, 32 * sizeof(int));
+  { const auto d = dbl_arrays(); for (size_t k = 0; k < d.size(); ++k) if (n) RX_HIP(hipMemcpy(d[k], hd[k].data(), sizeof(double) * n, hipMemcpyHostToDevice)); }
+  { const auto d = vec_arrays(); for (size_t k = 0; k < d.size(); ++k) if (n) RX_HIP(hipMemcpy(d[k], hv[k].data(), sizeof(double2) * n, hipMemcpyHostToDevice)); }
+  if (n) { RX_HIP(hipMemcpy(type, ht.data(), sizeof(int) * n, hipMemcpyHostToDevice)); RX_HIP(hipMemcpy(gid, hg.data(), sizeof(long long) * n, hipMemcpyHostToDevice)); }
+  RX_HIP(hipMemcpy(scal, hs.data(), sizeof(double) * SCAL_N, hipMemcpyHostToDevice));
+  G = N;
+}
+
+void Engine::set_barostat(int mode, int axes, const double p0[3], double tau_fs, double bulk_GPa, int every, double max_strain) {
+  if (mode < 0 || mode > 2) throw EngineError(RXMD_E_ARG, "barostat mode must be 0 (off), 1 (isotropic) or 2 (per axis)");
+  if (mode != 0) {
+    if (!p0) throw EngineError(RXMD_E_ARG, "barostat: p0_GPa is NULL");
+    if (!(tau_fs > 0.0) || !(bulk_GPa > 0.0)) throw EngineError(RXMD_E_ARG, "barostat: tau_fs and bulk_modulus_GPa must be > 0");
+    if (every < 1) throw EngineError(RXMD_E_ARG, "barostat: every must be >= 1");
+    if (!(max_strain > 0.0 && max_strain <= 0.1)) throw EngineError(RXMD_E_ARG, "barostat: max_strain must be in (0, 0.1]");
+    if (mode == 2 && (axes < 1 || axes > 7)) throw EngineError(RXMD_E_ARG, "barostat: axes is a bit mask of x (1), y (2), z (4)");
+    if (mode == 2 && !lattice_orthorhombic(box.lat)) throw EngineError(RXMD_E_ARG, "the per-axis barostat (mode 2) needs an orthorhombic cell");
+    const int np0 = mode == 1 ? 1 : 3;             // (isotropic: p0_GPa[0] only)
+    for (int a = 0; a < np0; ++a) if (!std::isfinite(p0[a])) throw EngineError(RXMD_E_ARG, "barostat: p0_GPa must be finite");
+    for (int a = 0; a < 3; ++a) bar_p0[a] = p0[a < np0 ? a : 0];
+    bar_axes = mode == 2 ? axes : 7; bar_tau = tau_fs; bar_B = bulk_GPa; bar_every = every; bar_max = max_strain;
+  }
+  bar_mode = mode;
 }
 
 }  // namespace rxmd

@@ -53,7 +53,32 @@ class RxmdEngine:
         if rc != 0:
             raise RxmdError(rc, (self.L.rxmd_hip_last_error(None) or b"").decode())
         self.h = h
-        self.lattice = [float(x) for x in lattice]
+
+    @property
+    def lattice(self):
+        """the current lattice of the whole box: follows set_lattice and the barostat (what write_xyz / write_pdb / write_rxff write)"""
+        return self.get_lattice()
+
+    def get_lattice(self):
+        out = np.zeros(6)
+        self._chk(self.L.rxmd_hip_get_lattice(self.h, _ptr(out)))
+        return [float(x) for x in out]
+
+    def set_lattice(self, lat):
+        """new lattice of the whole box (collective); the residents keep their normalised coordinates"""
+        lat = np.ascontiguousarray(lat, np.float64).reshape(6)
+        self._chk(self.L.rxmd_hip_set_lattice(self.h, _ptr(lat)))
+
+    def set_barostat(self, mode, p0=0.0, tau_fs=100.0, bulk_modulus=15.0, every=1, max_strain=0.01, axes=7):
+        """Berendsen barostat inside step(): mode 0 off, 1 isotropic (p0 [GPa] a number), 2 per axis (p0 a number or three, axes a bit mask x=1 y=2 z=4)"""
+        p = np.broadcast_to(np.asarray(p0, np.float64), (3,)).copy()
+        self._chk(self.L.rxmd_hip_set_barostat(self.h, int(mode), int(axes), _ptr(p), float(tau_fs), float(bulk_modulus), int(every), float(max_strain)))
+
+    def barostat_state(self):
+        """last coupling: pressure tensor p6 (xx,yy,zz,yz,zx,xy) [GPa], mu[3], the volume it was computed at [A^3], couplings so far"""
+        p6 = np.zeros(6); mu = np.zeros(3); vol = C.c_double(0); n = C.c_longlong(0)
+        self._chk(self.L.rxmd_hip_get_barostat(self.h, _ptr(p6), _ptr(mu), C.byref(vol), C.byref(n)))
+        return dict(p6=p6, mu=mu, volume=vol.value, couplings=n.value)
 
     def close(self):
         if getattr(self, "h", None):

@@ -1,0 +1,402 @@
+"""Variable cell: rxmd_hip_set_lattice on a live engine and the Berendsen barostat inside rxmd_hip_step, through the C ABI.
+
+A new lattice keeps every resident's normalised coordinates (r' = H' H^-1 r on the device) and derives the box-dependent set-up again,
+so QEq + FORCE after set_lattice(L1) must be what a fresh engine built at L1 from the same fractional input computes, and what the oracle
+computes there.  The barostat couples on the step's own stress sums (the astr that PRINTE prints) and scales the lattice lengths."""
+import os
+import socket
+import numpy as np
+import pytest
+
+import oracle_api as oa
+from test_gpu_parity import _engine, _oracle, q_err, f_err, e_err, QTOL, FTOL, ETOL
+
+pytestmark = pytest.mark.gpu
+
+GPA = 6.94728103          # main.F90:252
+TIGHT = dict(QEq_tol=1e-12, NMAXQEq=2000)
+
+
+def _fresh(case, mc, lat, **kw):
+    """an engine built at `lat` from the same fractional input (geninit's normalised records)"""
+    import rxmd_amd
+    from rxmd_amd import system
+    ff, names, frac, lat0 = oa.make_system(case)
+    _, rec = system.geninit(ff, names, frac, lat0, mc=mc)
+    e = rxmd_amd.RxmdEngine(ff, lat, **kw)
+    e.set_atoms_rxff(rec)
+    return e
+
+
+def _volume(lat):
+    a, b, c = lat[:3]
+    ca, cb, cg = np.cos(np.radians(lat[3:6]))
+    return a * b * c * np.sqrt(1.0 - ca * ca - cb * cb - cg * cg + 2.0 * ca * cb * cg)
+
+
+def _hmat(lat):
+    """GetBoxParams (init.F90:610-633): columns are the lattice vectors"""
+    la, lb, lc = lat[:3]
+    al, be, ga = np.radians(lat[3:6])
+    hh1 = lc * (np.cos(al) - np.cos(be) * np.cos(ga)) / np.sin(ga)
+    hh2 = lc * np.sqrt(1.0 - np.cos(al) ** 2 - np.cos(be) ** 2 - np.cos(ga) ** 2 + 2 * np.cos(al) * np.cos(be) * np.cos(ga)) / np.sin(ga)
+    return np.array([[la, lb * np.cos(ga), lc * np.cos(be)], [0.0, lb * np.sin(ga), hh1], [0.0, 0.0, hh2]])
+
+
+def _by_gid(a):
+    o = np.argsort(a["gid"])
+    return {k: v[o] for k, v in a.items()}
+
+
+def _same(a, b, tol):
+    """largest deviation of b from a, relative to the largest magnitude of a"""
+    return np.abs(a - b).max() / max(np.abs(a).max(), 1e-300) <= tol
+
+
+@pytest.mark.parametrize("case,mc,scale", [("rdx222", (2, 2, 2), (0.97, 0.97, 0.97)), ("rdx222", (2, 2, 2), (1.04, 1.04, 1.04)),
+                                           ("ice644", (6, 4, 4), (0.98, 1.00, 1.03)), ("mos2_tri324", (3, 3, 2), (0.98, 0.98, 0.98))])
+def test_set_lattice_equals_a_fresh_engine_and_the_oracle(case, mc, scale):
+    e = _engine(case, mc, **TIGHT)
+    L0 = e.lattice
+    L1 = [L0[a] * scale[a] for a in range(3)] + L0[3:]
+    e.QEq(); e.FORCE(); e.energy()                       # a live engine: lists, charges and accumulators of L0 exist
+    q0 = e.atoms()["q"]
+    e.set_lattice(L1)
+    assert e.lattice == L1
+    e.QEq(); pe = e.FORCE(); a = e.atoms(); astr = e.energy()["astr"]
+    st = e.stats()
+    f = _fresh(case, mc, L1, **TIGHT)
+    f.set_charges(q0)                                    # the same CG start vector as the live engine
+    f.QEq(); pf = f.FORCE(); b = f.atoms(); bstr = f.energy()["astr"]
+    assert (a["gid"] == b["gid"]).all()
+    assert _same(b["pos"], a["pos"], 1e-13)
+    assert q_err(a["q"], b["q"]) <= 1e-8 and f_err(a["f"], b["f"]) <= 1e-8
+    assert e_err(pe, pf) <= 1e-10
+    assert _same(bstr, astr, 1e-9)
+    sf = f.stats()
+    assert st["cells10"] == sf["cells10"] and st["cells3"] == sf["cells3"]
+    f.close()
+    ff, names, frac, lat = oa.make_system(case)
+    _, ranks = oa.geninit(names, frac, lat, oa.ffield_names(ff), mc=mc)
+    o = oa.Oracle(ff, L1, ranks, **TIGHT); o.qeq(); o.force()
+    assert (a["gid"] == o.gids()).all()
+    assert q_err(a["q"], o.charges()) <= QTOL
+    assert f_err(a["f"], o.forces()) <= FTOL
+    assert e_err(pe, o.energy()) <= ETOL
+    ostr = o.astr(reset=True)
+    assert np.abs(astr - ostr).max() <= 1e-9 * np.abs(ostr).max()
+    e.close()
+
+
+def test_capacity_grows_in_place_and_the_run_equals_an_engine_built_at_the_new_lattice():
+    """z compressed below 5 bond cut-offs: cc_z drops 5 -> 4, the normalised ghost shell widens and the engine needs more atom slots than
+    set-up gave it.  It grows in place (velocities, forces, charges, step count, accumulators kept) and 5 NVE steps equal an engine built
+    at the new lattice with room to spare; set back to L0 the positions come back."""
+    e = _engine("rdx222", (2, 2, 2), **TIGHT)
+    _, maxrc = e.cutoffs()
+    L0 = e.lattice
+    cc0 = [int(L0[a] / maxrc) for a in range(3)]
+    sz = (cc0[2] * maxrc - 0.05) / L0[2]
+    L1 = L0[:2] + [L0[2] * sz] + L0[3:]
+    e.thermostat(0, 300.0)
+    e.QEq(); e.FORCE()
+    st0 = e.stats(); p0 = e.atoms()
+    e.set_lattice(L1)
+    st1 = e.stats()
+    assert st1["cells3"] != st0["cells3"] and st1["cells3"][2] == cc0[2] - 1
+    assert st1["nbuffer"] > st0["nbuffer"]
+    a1 = e.atoms()
+    assert (a1["v"] == p0["v"]).all() and (a1["f"] == p0["f"]).all() and (a1["q"] == p0["q"]).all()
+    e.set_lattice(L0)
+    assert _same(p0["pos"], e.atoms()["pos"], 1e-13)
+    e.set_lattice(L1)
+    q1 = e.atoms()["q"]
+    e.QEq(); e.FORCE(); e.step(5)
+    a = _by_gid(e.atoms()); pe = e.FORCE()
+    f = _fresh("rdx222", (2, 2, 2), L1, nbuffer=4 * st1["nbuffer"], **TIGHT)
+    f.thermostat(0, 300.0); f.set_charges(q1)
+    f.QEq(); f.FORCE(); f.step(5)
+    b = _by_gid(f.atoms()); pf = f.FORCE()
+    assert f.stats()["nbuffer"] == 4 * st1["nbuffer"]
+    assert (a["gid"] == b["gid"]).all()
+    for k in ("pos", "v", "f", "q"):
+        assert _same(b[k], a[k], 1e-10), k
+    assert e_err(pe, pf) <= 1e-10
+    e.close(); f.close()
+
+
+def _strain_check(case, mc, eps=1e-5, fixed_q_eps=(1e-5, 1e-3, 1e-2)):
+    """virial W_aa = sum r_a f_a of a static crystal against -dE/d(eps_a) by central differences through set_lattice: with the charges
+    equilibrated again at every strained box (eps), and with the charges of the unstrained box kept (each of fixed_q_eps): (W, [3, 14],
+    {eps: [3, 14]}, V), per energy term"""
+    e = _engine(case, mc, **TIGHT)
+    L0 = e.lattice
+    e.QEq(); e.FORCE()
+    q0 = e.atoms()["q"]
+    W = e.energy()["astr"][:3].copy()
+    fd = np.zeros((3, 14)); fdq = {h: np.zeros((3, 14)) for h in fixed_q_eps}
+    for a in range(3):
+        E = []
+        for s in (+1, -1):
+            L = list(L0); L[a] = L0[a] * (1.0 + s * eps)
+            e.set_lattice(L); e.QEq(); E.append(e.FORCE())
+        fd[a] = -(E[0] - E[1]) / (2.0 * eps)
+        for h in fixed_q_eps:
+            Eq = []
+            for s in (+1, -1):
+                L = list(L0); L[a] = L0[a] * (1.0 + s * h)
+                e.set_lattice(L); e.set_charges(q0); Eq.append(e.FORCE())
+            fdq[h][a] = -(Eq[0] - Eq[1]) / (2.0 * h)
+    e.set_lattice(L0)
+    e.close()
+    return W, fd, fdq, _volume(L0)
+
+
+def test_virial_is_minus_the_strain_derivative_of_the_energy():
+    """The virial path against the energy.  With the charges equilibrated again at each strained box -dE/deps differs from the fixed-charge
+    derivative by sum_i (dE/dq_i)(dq_i/deps) (measured 0.04 GPa on ice644: Ecoulomb + Echarge).  At fixed charges and eps = 1e-5 the
+    derivative sees the tabulated vdW / Coulomb energies (r^2 tables, lerp between nodes 0.02 A^2 apart) as straight segments, while the forces
+    come from the tabulated derivative: the two disagree node interval by node interval (measured 0.6-1.4 % on ice644).  Over a strain
+    that spans several node intervals (eps = 1e-2) the secants average out and the virial must agree: gated there at 0.5 % or 0.01 GPa on
+    ice644 (no hydrogen-bond term, no hard cut-off).  rdx222 is reported only: its hydrogen-bond distance cut-off is not tapered."""
+    names = ["Esystem", "Ebond", "Elp", "Eover", "Eunder", "Eval", "Epen", "Ecoa", "Etors", "Econj", "Ehbond", "Evdwaals", "Ecoulomb", "Echarge"]
+    for case, mc, gate in (("ice644", (6, 4, 4), True), ("rdx222", (2, 2, 2), False)):
+        W, fd, fdq, V = _strain_check(case, mc)
+        pw = W / V * GPA
+        print("%s  P_aa [GPa] from astr %s ; -dE/deps/V with QEq at every box (eps 1e-5) %s" % (case, pw, fd[:, 0] / V * GPA))
+        for h, d in fdq.items():
+            print("   fixed q, eps %g: total %s   Evdwaals %s   Ecoulomb %s" % (h, d[:, 0] / V * GPA, d[:, 11] / V * GPA, d[:, 12] / V * GPA))
+        for k in range(1, 14):
+            print("   %-9s -dE/deps/V [GPa] fixed q eps 1e-5 %s   QEq %s" % (names[k], fdq[1e-5][:, k] / V * GPA, fd[:, k] / V * GPA))
+        assert np.isfinite(pw).all() and all(np.isfinite(d).all() for d in fdq.values())
+        if gate:
+            p2 = fdq[1e-2][:, 0] / V * GPA
+            assert (np.abs(pw - p2) <= np.maximum(0.005 * np.abs(p2), 0.01)).all(), (pw, p2)
+
+
+def test_barostat_off_changes_nothing():
+    """mode 0 (the default) launches nothing new: 10 NVE steps bit for bit those of an engine never configured"""
+    runs = []
+    for configure in (False, True):
+        e = _engine("rdx222", (2, 2, 2), **TIGHT)
+        if configure:
+            e.set_barostat(1, p0=0.0, tau_fs=100.0, bulk_modulus=15.0)
+            e.set_barostat(0)
+        e.thermostat(0, 300.0); e.QEq(); e.FORCE(); e.step(10)
+        runs.append((e.atoms(), e.FORCE(), e.lattice, e.barostat_state()))
+        e.close()
+    (a, pa, la, _), (b, pb, lb, sb) = runs
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    assert np.abs(pa - pb).max() <= 1e-12 * abs(pa[0]) and la == lb and sb["couplings"] == 0   # (energies are summed with atomics)
+
+
+def _mu_np(p6, mode, p0, rate, B, max_strain, axes=7):
+    mu = np.ones(3)
+    for k in range(3):
+        if mode == 1:
+            mu[k] = np.cbrt(1.0 - rate * (p0[0] - (p6[0] + p6[1] + p6[2]) / 3.0) / B)
+        elif (axes >> k) & 1:
+            mu[k] = np.cbrt(1.0 - rate * (p0[k] - p6[k]) / B)
+    return np.clip(mu, 1.0 - max_strain, 1.0 + max_strain)
+
+
+def _coupled_run(qeq_mode, tau, max_strain, read_every_step, nsteps=5):
+    e = _engine("rdx222", (2, 2, 2), qeq_mode=qeq_mode, **TIGHT)
+    e.thermostat(0, 300.0); e.QEq(); e.FORCE(); e.energy()
+    e.set_barostat(1, p0=0.0, tau_fs=tau, bulk_modulus=15.0, every=1, max_strain=max_strain)
+    rows = []
+    for k in range(nsteps):
+        lat = e.lattice
+        e.step(1)
+        rows.append(dict(lat=lat, new=e.lattice, astr=e.energy()["astr"] if read_every_step else None, **e.barostat_state()))
+    e.close()
+    return rows
+
+
+@pytest.mark.parametrize("qeq_mode,tau,max_strain,clamped", [(0, 25.0, 0.1, False), (1, 25.0, 0.1, False), (0, 0.5, 1e-5, True)])
+def test_coupling_arithmetic(qeq_mode, tau, max_strain, clamped):
+    """every = 1: the reported tensor is that step's astr / V * 6.94728103 (V before the remap), mu follows from it, the new lattice is the old
+    one times mu; with a tiny max_strain the clamp shows.  A second run that never reads (nor resets) astr couples to the same pressures: the
+    barostat's own sums are the step's, whatever astr has accumulated and whatever the CG loop (either qeq_mode) stores meanwhile."""
+    rows = _coupled_run(qeq_mode, tau, max_strain, True)
+    n_clamped = 0
+    for k, r in enumerate(rows):
+        assert r["couplings"] == k + 1
+        assert abs(r["volume"] - _volume(r["lat"])) <= 1e-13 * r["volume"]
+        p6 = r["astr"] / r["volume"] * GPA
+        assert np.abs(r["p6"] - p6).max() <= 1e-12 * np.abs(p6).max()
+        mu = _mu_np(r["p6"], 1, [0.0, 0.0, 0.0], 0.25 / tau, 15.0, max_strain)
+        assert np.abs(r["mu"] - mu).max() <= 1e-14
+        assert r["mu"][0] == r["mu"][1] == r["mu"][2]
+        assert all(abs(r["new"][a] - r["lat"][a] * r["mu"][a]) <= 1e-14 * r["lat"][a] for a in range(3)) and r["new"][3:] == r["lat"][3:]
+        n_clamped += abs(abs(r["mu"][0] - 1.0) - max_strain) < 1e-15
+    assert (n_clamped == 5) if clamped else (n_clamped == 0)
+    quiet = _coupled_run(qeq_mode, tau, max_strain, False)
+    for r, u in zip(rows, quiet):
+        assert np.abs(u["p6"] - r["p6"]).max() <= 1e-9 * np.abs(r["p6"]).max()
+        assert max(abs(u["new"][a] - r["new"][a]) for a in range(3)) <= 1e-13 * r["new"][0]
+
+
+def _relax(qeq_mode, thermostat, L0, nsteps=400):
+    e = _engine("rdx222", (2, 2, 2), qeq_mode=qeq_mode, **TIGHT)
+    e.set_lattice([x * 0.97 for x in L0[:3]] + L0[3:])
+    e.thermostat(0, 10.0); e.QEq(); e.FORCE()
+    e.set_barostat(1, p0=0.0, tau_fs=25.0, bulk_modulus=15.0, every=1, max_strain=0.01)
+    P = []
+    for k in range(nsteps):
+        if k % 10 == 0 and thermostat:
+            e.thermostat(5, 10.0)                        # the host loop of the header (sstep 10): the crystal stays at 10 K
+        e.step(1)
+        P.append(e.barostat_state()["p6"][:3].mean())
+    T = e.energy()["KE"] / e.natoms * 503.398008 * 2.0 / 3.0
+    V = _volume(e.lattice)
+    e.close()
+    return np.array(P), T, V
+
+
+def test_berendsen_relaxation_from_three_percent_compression():
+    """rdx222 3 % compressed (affinely: its bonds are squeezed with the box, P = 111 GPa), 10 K, P0 = 0, tau 25 fs, B 15 GPa, 400 steps: |P|
+    falls to 0.2 of its start, with either CG algebra.  Kept at 10 K by rxmd_hip_thermostat every 10 steps (the header's host loop) the crystal
+    ends at a smaller volume than without it, where the released compression heats it (measured 87 K) and its thermal pressure moves the zero
+    of pressure outward.  Mode 2 with axes = 4 moves c only: a and b keep their lengths bit for bit."""
+    L0 = _engine("rdx222", (2, 2, 2)).lattice
+    runs = {(m, t): _relax(m, t, L0) for m, t in ((0, True), (1, True), (0, False))}
+    for (m, t), (P, T, V) in runs.items():
+        print("qeq_mode %d, thermostat %s: P start %.4f GPa, mean of the last 50 steps %.4f GPa, T end %.1f K, V end %.2f (V of the input crystal %.2f)"
+              % (m, t, P[0], P[-50:].mean(), T, V, _volume(L0)))
+        assert abs(P[-50:].mean()) <= 0.2 * abs(P[0])
+    (_, T0, V0), (_, T1, V1), (_, Th, Vh) = runs[(0, True)], runs[(1, True)], runs[(0, False)]
+    assert T0 < 15.0 and T1 < 15.0 and Th > 30.0
+    assert abs(V1 - V0) <= 1e-6 * V0                     # the two CG algebras reach the same charges: the same run
+    assert Vh > V0
+    e = _engine("rdx222", (2, 2, 2), **TIGHT)
+    e.set_lattice([x * 0.97 for x in L0[:3]] + L0[3:])
+    Lc = e.lattice
+    e.thermostat(0, 10.0); e.QEq(); e.FORCE()
+    e.set_barostat(2, p0=(0.0, 0.0, 0.0), tau_fs=25.0, bulk_modulus=15.0, every=1, max_strain=0.01, axes=4)
+    e.step(20)
+    L = e.lattice
+    assert L[0] == Lc[0] and L[1] == Lc[1] and L[2] > Lc[2]
+    assert e.barostat_state()["couplings"] == 20
+    e.close()
+
+
+def test_rejections_keep_the_old_lattice():
+    from rxmd_amd import RxmdError
+    e = _engine("mos2_tri324", (3, 3, 2), **TIGHT)
+    e.QEq(); pe0 = e.FORCE()
+    L0 = e.lattice
+    _, maxrc = e.cutoffs()
+    bad = [[-L0[0]] + L0[1:], L0[:3] + [90.0, 90.0, 180.0], L0[:3] + [120.0, 120.0, 120.0], [L0[0], L0[1], 0.9 * maxrc] + L0[3:]]
+    for L in bad:
+        with pytest.raises(RxmdError) as ex:
+            e.set_lattice(L)
+        assert ex.value.code == -1
+        assert e.lattice == L0
+    for kw in (dict(tau_fs=0.0), dict(bulk_modulus=-1.0), dict(every=0), dict(max_strain=0.0), dict(max_strain=0.2)):
+        with pytest.raises(RxmdError):
+            e.set_barostat(1, **kw)
+    with pytest.raises(RxmdError):
+        e.set_barostat(2, p0=(0, 0, 0))                  # gamma = 120 degrees: per axis is for orthorhombic cells
+    e.QEq()
+    assert np.abs(e.FORCE() - pe0).max() <= 1e-9 * abs(pe0[0])
+    e.close()
+
+
+def test_checkpoint_after_barostat_steps(tmp_path):
+    """write_rxff after barostat steps carries the current lattice; an engine built from the file computes what the live one computes"""
+    import rxmd_amd
+    from rxmd_amd import system
+    e = _engine("rdx222", (2, 2, 2), **TIGHT)
+    e.thermostat(0, 300.0); e.QEq(); e.FORCE()
+    e.set_barostat(1, p0=1.0, tau_fs=25.0, bulk_modulus=15.0, every=2, max_strain=0.01)
+    e.step(6)
+    assert e.barostat_state()["couplings"] == 3
+    path = str(tmp_path / "rxff.bin")
+    e.write_rxff(path)
+    lat, vp, rec = system.read_rxff(path)
+    assert lat == e.get_lattice()
+    f = rxmd_amd.RxmdEngine(oa.make_system("rdx222")[0], lat, **TIGHT)
+    f.set_atoms_rxff(rec)
+    e.QEq(); pe = e.FORCE(); a = _by_gid(e.atoms())
+    f.QEq(); pf = f.FORCE(); b = _by_gid(f.atoms())
+    assert (a["gid"] == b["gid"]).all()
+    assert _same(a["pos"], b["pos"], 1e-12)
+    assert q_err(b["q"], a["q"]) <= 1e-10 and f_err(b["f"], a["f"]) <= 1e-10
+    assert e_err(pf, pe) <= 1e-10
+    e.close(); f.close()
+
+
+def test_pqeq_shells_follow_the_lattice():
+    """PQEq: set_lattice maps the shell displacements with the same M = H' H^-1: a fresh engine at L1 given set_shells(M d) (and the same
+    charges) computes the same PQEq + FORCE"""
+    kw = dict(pqeq=oa.PQEQ_SICNP, **TIGHT)
+    e = _engine("sicnp547", (1, 1, 1), **kw)
+    L0 = e.lattice
+    e.QEq(); e.FORCE()
+    d = e.shells(); q = e.atoms()["q"]
+    L1 = [x * 0.98 for x in L0[:3]] + L0[3:]
+    e.set_lattice(L1)
+    M = _hmat(L1) @ np.linalg.inv(_hmat(L0))
+    assert _same(d @ M.T, e.shells(), 1e-13)
+    ie, ee = e.QEq(); pe = e.FORCE(); a = e.atoms(); te = e.debug(13, cap=4096)
+    assert ie > 0
+    f = _fresh("sicnp547", (1, 1, 1), L1, **kw)
+    f.set_shells(d @ M.T); f.set_charges(q)
+    i_f, ef = f.QEq(); pf = f.FORCE(); b = f.atoms(); tf = f.debug(13, cap=4096)
+    n = min(len(te), len(tf))
+    print("PQEq after set_lattice: CG iterations live %d fresh %d; Est live %.15e fresh %.15e; largest relative Est gap over the common "
+          "iterations %.3e; charges %.3e apart" % (ie, i_f, ee, ef, np.abs(te[:n] - tf[:n]).max() / np.abs(tf[:n]).max(), q_err(a["q"], b["q"])))
+    assert (a["gid"] == b["gid"]).all()
+    assert q_err(a["q"], b["q"]) <= QTOL and f_err(a["f"], b["f"]) <= FTOL
+    # measured: the same iteration count (18) and the same Est trace to 2e-13 relative, the charges 1.4e-7 apart (4.9e-8 at QEq_tol 1e-14):
+    # neither the start vector nor the exit test; what is left is the 1e-16 difference of the two inputs (positions through H'H^-1 on the
+    # device against H' s from the records, shells through the device's and numpy's M) carried through PQEq's coupled charge / shell solve
+    assert np.abs(pe - pf).max() <= 1e-9 * abs(pf[0])       # (the PQEq Coulomb term is what is left of large core / shell sums: gated on the total's scale)
+    e.close(); f.close()
+
+
+def _port():
+    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
+
+
+def test_two_ranks_couple_to_the_same_lattice():
+    """vprocs (2,1,1), two processes on one GPU over gloo.  The virial of the first FORCE summed over the two ranks is the one-rank virial and
+    the oracle's two-rank sum; 10 isotropic couplings give the same lattice on both ranks bit for bit, within 1e-12 of the one-rank run, energies
+    to 1e-9; a rank given another lattice makes set_lattice fail with RXMD_E_ARG on both"""
+    import torch.multiprocessing as mp
+    import vc_worker
+    ctx = mp.get_context("spawn")
+    with ctx.Manager() as m:
+        out = m.dict()
+        port = _port()
+        ps = [ctx.Process(target=vc_worker.barostat_rank, args=(r, 2, port, 10, out)) for r in range(2)]
+        [p.start() for p in ps]; [p.join(600) for p in ps]
+        assert len(out) == 2, "a rank died"
+        res = [out[r] for r in range(2)]
+    for o in res:
+        assert "error" not in o, o.get("error")
+    one = vc_worker.barostat_run((1, 1, 1), 0, 10)
+    ff, names, frac, lat = oa.make_system("rdx222")
+    lat2, ranks = oa.geninit(names, frac, lat, oa.ffield_names(ff), mc=(2, 2, 2), vprocs=(2, 1, 1))
+    o = oa.Oracle(ff, lat2, ranks, vprocs=(2, 1, 1), **TIGHT); o.qeq(); o.force()
+    ostr2 = o.astr(reset=True)
+    _, ranks1 = oa.geninit(names, frac, lat, oa.ffield_names(ff), mc=(2, 2, 2))
+    o1 = oa.Oracle(ff, lat2, ranks1, **TIGHT); o1.qeq(); o1.force()
+    ostr1 = o1.astr(reset=True)
+    a2, a1 = np.array(res[0]["astr0"]) + np.array(res[1]["astr0"]), np.array(one["astr0"])
+    l0, l1 = np.array(res[0]["lattices"]), np.array(res[1]["lattices"])
+    dl = np.abs(l0 - np.array(one["lattices"])).max() / np.abs(l0).max()
+    pe, pe0 = np.array(res[0]["pe"]) + np.array(res[1]["pe"]), np.array(res[0]["pe0"]) + np.array(res[1]["pe0"])
+    print("virial of the first FORCE: engine two ranks %s oracle two ranks %s ; engine one rank %s oracle one rank %s" % (a2, ostr2, a1, ostr1))
+    print("two ranks against one: energies of the first FORCE %.3e; after 10 couplings lattice %.3e relative, energies %.3e" % (e_err(pe0, one["pe0"]), dl, e_err(pe, one["pe"])))
+    # The stress sums are the reference's: each decomposition's astr is the oracle's for that decomposition (the oracle is pinned to the real
+    # reference), and the reference's own two-rank sum is NOT its one-rank sum (measured 1.8 % on xx).  The barostat couples to what PRINTE
+    # prints, so its pressure -- and the lattice it drives -- depend on the decomposition as the reference's printed pressure does.
+    assert np.abs(a2 - ostr2).max() <= 1e-9 * np.abs(ostr2).max()
+    assert np.abs(a1 - ostr1).max() <= 1e-9 * np.abs(ostr1).max()
+    assert e_err(pe0, one["pe0"]) <= 1e-9
+    assert np.array_equal(l0, l1)
+    assert res[0]["mismatch_rc"] == -1 and res[1]["mismatch_rc"] == -1
+    assert res[0]["lattice_after_mismatch"] == res[0]["lattices"][-1]
