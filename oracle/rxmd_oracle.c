@@ -1944,19 +1944,15 @@ int rxo_set_atoms(void *w, int rank, int n, const double *rnorm, const double *v
   return 0;
 }
 
-int rxo_init(void *w) { /* the rest of INITSYSTEM: cutoffs, cells, tables, 10 A mesh */
-  World *W = (World *)w; Params *P = &W->P;
-  long long *npt = (long long *)calloc(P->nso + 2, sizeof(long long));
-  W->GNATOMS = 0;
-  for (int p = 0; p < W->nprocs; p++) { Rank *r = &W->R[p]; W->GNATOMS += r->NATOMS; for (int i = 1; i <= r->NATOMS; i++) npt[r->ity[i]]++; }
-  cutofflength(P, npt);
-  free(npt);
+/* The box-dependent half of INITSYSTEM: bond cells (UpdateBoxParams, init.F90:636-668), the 10 A mesh (GetNonbondingMesh, init.F90:525-607) and
+ * the per-rank cell headers.  rxo_init runs it once; rxo_set_lattice runs it again at every new lattice. */
+static void derive_box_cells(World *W) {
+  Params *P = &W->P;
   double lb[3] = {W->lata / W->vprocs[0], W->latb / W->vprocs[1], W->latc / W->vprocs[2]};
-  for (int a = 0; a < 3; a++) { W->cc[a] = (int)(lb[a] / P->maxrc); W->lcsize[a] = W->LBOX[a + 1] / W->cc[a]; } /* UpdateBoxParams, init.F90:636-668 */
-  potentialtable(P);
-  /* GetNonbondingMesh, init.F90:525-607 */
+  for (int a = 0; a < 3; a++) { W->cc[a] = (int)(lb[a] / P->maxrc); W->lcsize[a] = W->LBOX[a + 1] / W->cc[a]; }
   double nbl[3]; int imesh[3];
   for (int a = 0; a < 3; a++) { W->nbcc[a] = (int)(lb[a] / 3.0); nbl[a] = lb[a] / W->nbcc[a]; imesh[a] = (int)(P->rctap / nbl[a]) + 1; }
+  free(W->nbmesh); W->nbmesh = NULL;
   for (int pass = 0; pass < 2; pass++) {
     int cnt = 0;
     for (int i = -imesh[0]; i <= imesh[0]; i++) for (int j = -imesh[1]; j <= imesh[1]; j++) for (int k = -imesh[2]; k <= imesh[2]; k++) {
@@ -1974,11 +1970,58 @@ int rxo_init(void *w) { /* the rest of INITSYSTEM: cutoffs, cells, tables, 10 A 
     Rank *r = &W->R[p];
     size_t nc = (size_t)(W->cc[0] + 2 * MAXLAYERS) * (W->cc[1] + 2 * MAXLAYERS) * (W->cc[2] + 2 * MAXLAYERS);
     size_t nnb = (size_t)(W->nbcc[0] + 2 * MAXLAYERS_NB) * (W->nbcc[1] + 2 * MAXLAYERS_NB) * (W->nbcc[2] + 2 * MAXLAYERS_NB);
+    free(r->header); free(r->nacell); free(r->nbheader); free(r->nbnacell);
     r->header = ialloc(nc); r->nacell = ialloc(nc); r->nbheader = ialloc(nnb); r->nbnacell = ialloc(nnb);
+  }
+}
+
+int rxo_init(void *w) { /* the rest of INITSYSTEM: cutoffs, cells, tables, 10 A mesh */
+  World *W = (World *)w; Params *P = &W->P;
+  long long *npt = (long long *)calloc(P->nso + 2, sizeof(long long));
+  W->GNATOMS = 0;
+  for (int p = 0; p < W->nprocs; p++) { Rank *r = &W->R[p]; W->GNATOMS += r->NATOMS; for (int i = 1; i <= r->NATOMS; i++) npt[r->ity[i]]++; }
+  cutofflength(P, npt);
+  free(npt);
+  potentialtable(P);
+  derive_box_cells(W);
+  for (int p = 0; p < W->nprocs; p++) {
+    Rank *r = &W->R[p];
     size_t rows = (size_t)r->NATOMS + (size_t)(r->NATOMS / 4) + 64;   /* residents may grow by migration */
     if (rows > (size_t)r->NBUFFER) rows = r->NBUFFER;
     r->nbplist = ialloc(rows * (r->maxn10 + 1)); r->hessian = dalloc(rows * (r->maxn10 + 1));
   }
+  return 0;
+}
+
+/* Variable cell (no counterpart in the reference, whose box is fixed at start-up): what rxmd_hip_set_lattice does to a live engine, in plain C.
+ * Every rank's residents keep their normalised coordinates (xu2xs with the old box, GetBoxParams, xs2xu with the new one); the PQEq shell
+ * displacements follow the same linear map M = H' H^-1 (they are displacements, so no origin); cc, lcsize, nbcc, the 10 A mesh, nblcsize and
+ * the cell headers are derived again by the routine rxo_init uses.  Velocities, forces, charges, qsfp / qsfv, astr and the step count are
+ * untouched: the first half-kick after a lattice change uses the forces of the old box, as the engine's does.
+ * Returns non-zero (rxo_error says why, nothing changed) for a lattice that spans no box or whose local box is shorter than maxrc. */
+int rxo_set_lattice(void *w, const double lattice[6]) {
+  World *W = (World *)w; Params *P = &W->P;
+  double pi = atan(1.0) * 4.0, ca = cos(lattice[3] * pi / 180.0), cb = cos(lattice[4] * pi / 180.0), cg = cos(lattice[5] * pi / 180.0);
+  int ok = 1;
+  for (int a = 0; a < 3; a++) ok = ok && lattice[a] > 0.0 && lattice[3 + a] > 0.0 && lattice[3 + a] < 180.0;
+  if (!ok || !(1.0 - ca * ca - cb * cb - cg * cg + 2.0 * ca * cb * cg > 1e-12)) { snprintf(W->err, 256, "set_lattice: the lattice does not span a box"); return -1; }
+  for (int a = 0; a < 3; a++)
+    if ((int)(lattice[a] / W->vprocs[a] / P->maxrc) < 1) { snprintf(W->err, 256, "set_lattice: local box edge %d (%g) is shorter than maxrc (%g)", a, lattice[a] / W->vprocs[a], P->maxrc); return -1; }
+  double Hi0[3][3], M[3][3];
+  memcpy(Hi0, W->HHi, sizeof(Hi0));
+  for (int p = 0; p < W->nprocs; p++) xu2xs_inplace(W, &W->R[p], W->R[p].NATOMS);
+  W->lata = lattice[0]; W->latb = lattice[1]; W->latc = lattice[2]; W->lalpha = lattice[3]; W->lbeta = lattice[4]; W->lgamma = lattice[5];
+  get_box(W);
+  for (int p = 0; p < W->nprocs; p++) xs2xu_inplace(W, &W->R[p], W->R[p].NATOMS);
+  for (int a = 0; a < 3; a++) for (int b = 0; b < 3; b++) M[a][b] = W->HH[a][0] * Hi0[0][b] + W->HH[a][1] * Hi0[1][b] + W->HH[a][2] * Hi0[2][b];
+  if (P->isPQEq)
+    for (int p = 0; p < W->nprocs; p++) { Rank *r = &W->R[p];
+      for (int i = 1; i <= r->NATOMS; i++) {
+        double d[3] = {SPOS(r, i, 0), SPOS(r, i, 1), SPOS(r, i, 2)};
+        for (int a = 0; a < 3; a++) SPOS(r, i, a) = M[a][0] * d[0] + M[a][1] * d[1] + M[a][2] * d[2];
+      }
+    }
+  derive_box_cells(W);
   return 0;
 }
 
@@ -2028,7 +2071,7 @@ double rxo_kinetic(void *w) { /* PRINTE, main.F90:225-229 */
   for (int p = 0; p < W->nprocs; p++) { Rank *r = &W->R[p]; for (int i = 1; i <= r->NATOMS; i++) KE += W->hmas[r->ity[i]] * (VEL(r, i, 0) * VEL(r, i, 0) + VEL(r, i, 1) * VEL(r, i, 1) + VEL(r, i, 2) * VEL(r, i, 2)); }
   return KE;
 }
-/* per-atom arrays of residents (n) or residents+ghosts (what >= 100): 0 pos(3) 1 v(3) 2 f(3) 3 q 4 type 5 gid 6 qs 7 qt
+/* per-atom arrays of residents (n) or residents+ghosts (what >= 100): 0 pos(3) 1 v(3) 2 f(3) 3 q 4 type 5 gid 6 qs 7 qt 8 spos(3) 9 fpqeq 10 qsfp 11 qsfv
  * 100 pos incl ghosts, 101 delta, 102 deltap1, 103 nbr count, 104 n10 count, 105 type incl ghosts, 106 gid incl ghosts, 107 cdbnd? (after force: zero) */
 int rxo_get(void *w, int rank, int what, double *out) {
   World *W = (World *)w; Rank *r = &W->R[rank];
@@ -2044,6 +2087,8 @@ int rxo_get(void *w, int rank, int what, double *out) {
     case 7: for (int i = 1; i <= n; i++) out[i - 1] = r->qt[i]; return n;
     case 8: for (int i = 1; i <= n; i++) for (int k = 0; k < 3; k++) out[3 * (i - 1) + k] = SPOS(r, i, k); return n;
     case 9: for (int i = 1; i <= n; i++) out[i - 1] = r->fpqeq[i]; return n;
+    case 10: for (int i = 1; i <= n; i++) out[i - 1] = r->qsfp[i]; return n;
+    case 11: for (int i = 1; i <= n; i++) out[i - 1] = r->qsfv[i]; return n;
     case 100: for (int i = 1; i <= G; i++) for (int k = 0; k < 3; k++) out[3 * (i - 1) + k] = POS(r, i, k); return G;
     case 101: for (int i = 1; i <= G; i++) out[i - 1] = r->delta[i]; return G;
     case 102: for (int i = 1; i <= G; i++) out[i - 1] = r->deltap[2 * i]; return G;
@@ -2069,5 +2114,9 @@ int rxo_get_bonds(void *w, int rank, int *nbr, double *bo0) {
 /* qsfp / qsfv of a restart file (rxff.bin record columns 9-10, fileio.F90:536-537) */
 void rxo_set_lex(void *w, int rank, const double *qsfp, const double *qsfv) { World *W = (World *)w; Rank *r = &W->R[rank]; for (int i = 1; i <= r->NATOMS; i++) { r->qsfp[i] = qsfp[i - 1]; r->qsfv[i] = qsfv[i - 1]; } }
 void rxo_set_charges(void *w, int rank, const double *q) { World *W = (World *)w; Rank *r = &W->R[rank]; for (int i = 1; i <= r->NATOMS; i++) r->q[i] = q[i - 1]; }
+/* PQEq shell displacements of the residents, [n][3] (a restart of a state whose shells have moved) */
+void rxo_set_shells(void *w, int rank, const double *d) { World *W = (World *)w; Rank *r = &W->R[rank]; for (int i = 1; i <= r->NATOMS; i++) for (int k = 0; k < 3; k++) SPOS(r, i, k) = d[3 * (i - 1) + k]; }
+/* Cartesian positions of the residents, [n][3], as they are (no normalised detour): two oracles can be given bit-equal coordinates */
+void rxo_set_pos(void *w, int rank, const double *x) { World *W = (World *)w; Rank *r = &W->R[rank]; for (int i = 1; i <= r->NATOMS; i++) for (int k = 0; k < 3; k++) POS(r, i, k) = x[3 * (i - 1) + k]; }
 void rxo_set_qeq(void *w, int isQEq, int NMAXQEq, double tol) { World *W = (World *)w; W->isQEq = isQEq; W->NMAXQEq = NMAXQEq; W->QEq_tol = tol; }
 void rxo_destroy(void *w) { (void)w; /* test processes are short-lived; leak on purpose */ }

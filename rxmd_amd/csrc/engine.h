@@ -407,6 +407,7 @@ struct Engine {
   void nonbonded(bool to_fnb = false);
   void pqeq_sorted_shells();      // ghost shells <- owners, cell-sorted copy (MODE_COPY payload of spos, comm.F90:129-131)
   void pqeq_update_shells();      // update_shell_positions, pqeq.F90:184-259
+  bool pq_matrix_stale = false;   // PQEq: the shells have moved (end of a PQEq call) since the 10 A list formed its shell-core values and field term from them
   void nonbonded_pqeq();          // ENbond_PQEq, pot.F90:784-923
   void efield_force();            // EEfield, module.F90:359-383
   void remove_momentum();         // LinearMomentum, main.F90:766-797

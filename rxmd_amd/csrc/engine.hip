@@ -419,9 +419,14 @@ void Engine::alloc_device() {
   partials_cap = std::max<size_t>(size_t(1) << 16, 4 * static_cast<size_t>(rows10) + 16384);   // up to one workgroup (4 partial sums) per row
   dmalloc(partials, partials_cap + 1024); dzalloc(scal, SCAL_N);   // + the 128 x 4 first-level sums of k_reduce_fused, behind the per-workgroup partials at a fixed offset
   RX_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_scal), 320 * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));   // coherent: the update kernel's tail stores the CG snapshot into it and the host polls it      // [0,64): as before; [64,192): the two slots of the run-ahead CG loop (qeq.hip); [192,288): the per-type sums of a host transport
+  // Pinned memory comes back from the allocator as the last owner left it, and a process may hold several engines one after another: a stale
+  // sequence word of an earlier engine's CG snapshot could satisfy wait_snapshot's poll.  Zeroed where it is allocated (set-up and grow_capacity
+  // both come through here).  Which block the allocator hands out is its choice, so no test can pin this.
+  std::memset(h_scal, 0, 320 * sizeof(double));
   dzalloc(tsum, 128); { double *sa_ = nullptr; dzalloc(sa_, 32); sargs = reinterpret_cast<ScaleArgs *>(sa_); }
   dzalloc(d_err, 16);
   RX_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_err), 32 * sizeof(int)));
+  std::memset(h_err, 0, 32 * sizeof(int));
   h_cnt = h_err + 16;
   // hipcub scratch sized for the largest scan / sort we issue
   size_t b1 = 0, b2 = 0;
@@ -1669,6 +1674,7 @@ void Engine::build_ghosts_and_lists(bool qeq_prepass) {
   collect_timers();
   outer_end(t_lists);
   lists_valid = true;
+  pq_matrix_stale = false;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1776,8 +1782,7 @@ void Engine::apply_lattice(const double lat[6]) {
 }
 
 // Growth: the slow exact path.  The residents' state and the device scalars go through the host, every buffer is allocated again at the new
-// capacity as set-up allocates it, and the state comes back.  Re-allocated pinned memory is zeroed: a stale sequence word in h_scal / h_pub
-// could otherwise satisfy a later poll.
+// capacity as set-up allocates it (alloc_device zeroes the pinned blocks it allocates), and the state comes back.
 void Engine::grow_capacity(int new_nb) {
   if (new_nb >= (1 << NB10_IDX_BITS)) throw EngineError(RXMD_E_NBUFFER, "more than 2^26 atoms+ghosts per GPU do not fit the packed 10 A list entry");
   RX_HIP(hipDeviceSynchronize());                  // (every stream of the engine: the bonded chain and the halo stream included)
@@ -1801,8 +1806,6 @@ void Engine::grow_capacity(int new_nb) {
   NB = new_nb;
   alloc_device();
   upload_ff();
-  std::memset(h_scal, 0, 320 * sizeof(double));
-  std::memset(h_err, 0, 32 * sizeof(int));
   { const auto d = dbl_arrays(); for (size_t k = 0; k < d.size(); ++k) if (n) RX_HIP(hipMemcpy(d[k], hd[k].data(), sizeof(double) * n, hipMemcpyHostToDevice)); }
   { const auto d = vec_arrays(); for (size_t k = 0; k < d.size(); ++k) if (n) RX_HIP(hipMemcpy(d[k], hv[k].data(), sizeof(double2) * n, hipMemcpyHostToDevice)); }
   if (n) { RX_HIP(hipMemcpy(type, ht.data(), sizeof(int) * n, hipMemcpyHostToDevice)); RX_HIP(hipMemcpy(gid, hg.data(), sizeof(long long) * n, hipMemcpyHostToDevice)); }

@@ -113,6 +113,7 @@ void Engine::pqeq_update_shells() {
   double *tmp[3] = {cds, cd, cc_};
   for (int a = 0; a < 3; ++a) RX_HIP(hipMemcpyAsync(shl[a], tmp[a], sizeof(double) * N, hipMemcpyDeviceToDevice, stream));
   pqeq_sorted_shells();            // FORCE's MODE_COPY carries the moved shells to the ghosts (pot.F90:28)
+  pq_matrix_stale = true;          // the matrix rows of the 10 A list hold the OLD shells: a PQEq call before the atoms move again builds them anew
 }
 
 // ENbond_PQEq: van der Waals from the ReaxFF table; Coulomb between cores and shells of both atoms from the three PQEq

@@ -598,7 +598,9 @@ void Engine::qeq() {
   // the list sweep of this step can form the row sums of the start vector on the way (saves the matrix pass of qeq.F90:87)
   const bool prepass_on = !opt.qeq_no_prepass;      // (experiments build only)
   sums_from_list = false;
-  if (!lists_valid) build_ghosts_and_lists(prepass_on);
+  // PQEq: qeq_initialize forms the matrix from the shells as they are now (pqeq.F90:61); a call that follows another without the atoms having moved
+  // (no migration in between, so the lists are still valid) must not re-use the rows built from the shells of before the last update
+  if (!lists_valid || (ff.pqeq && pq_matrix_stale)) build_ghosts_and_lists(prepass_on);
   const int nmax = (cfg.isQEq == 1) ? cfg.NMAXQEq : 1;
   // one wavefront per row, sixteen rows per workgroup: measured faster than a persistent grid-stride launch (1.10 vs 1.28 ms
   // per pass at 979,776 rows) -- many short waves overlap each other's load / gather / reduce phases (NOTES.md 3, K4/K5)

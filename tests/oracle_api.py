@@ -29,7 +29,7 @@ def lib():
         L.rxo_error.restype = C.c_char_p
         L.rxo_kinetic.restype = C.c_double
         for f in ("rxo_set_atoms", "rxo_init", "rxo_qeq", "rxo_force", "rxo_step", "rxo_natoms", "rxo_nghost_total", "rxo_qeq_iters",
-                  "rxo_ntrace", "rxo_get", "rxo_get_bonds"):
+                  "rxo_ntrace", "rxo_get", "rxo_get_bonds", "rxo_set_lattice"):
             getattr(L, f).restype = C.c_int
         _lib = L
     return _lib
@@ -140,6 +140,7 @@ class Oracle:
     def forces(self, rank=0): return self.get(2, rank, 3)
     def charges(self, rank=0): return self.get(3, rank)
     def spos(self, rank=0): return self.get(8, rank, 3)
+    def lex(self, rank=0): return self.get(10, rank), self.get(11, rank)
     def set_efield(self, direction, strength):
         self.L.rxo_set_efield.argtypes = [C.c_void_p, C.c_int, C.c_double]; self.L.rxo_set_efield(self.w, int(direction), float(strength))
 
@@ -181,6 +182,26 @@ class Oracle:
 
     def set_charges(self, q, rank=0):
         q = np.ascontiguousarray(q, np.float64); self.L.rxo_set_charges(self.w, rank, q.ctypes.data_as(C.c_void_p))
+
+    def set_lattice(self, lattice):
+        """a new lattice on the live oracle (rxo_set_lattice): residents keep their normalised coordinates, PQEq shell displacements follow the
+        same linear map, the cells and the 10 A mesh are derived again; velocities, forces, charges, qsfp / qsfv, astr and the step count stay,
+        so the first half-kick after it uses the forces of the old box (the engine does the same).  RuntimeError for a rejected lattice."""
+        self.L.rxo_set_lattice.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        self._chk(self.L.rxo_set_lattice(self.w, (C.c_double * 6)(*[float(x) for x in lattice])))
+
+    def set_lex(self, qsfp, qsfv, rank=0):
+        a = np.ascontiguousarray(qsfp, np.float64); b = np.ascontiguousarray(qsfv, np.float64)
+        self.L.rxo_set_lex.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self.L.rxo_set_lex(self.w, rank, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p))
+
+    def set_shells(self, d, rank=0):
+        d = np.ascontiguousarray(d, np.float64); assert d.shape == (self.L.rxo_natoms(self.w, rank), 3)
+        self.L.rxo_set_shells.argtypes = [C.c_void_p, C.c_int, C.c_void_p]; self.L.rxo_set_shells(self.w, rank, d.ctypes.data_as(C.c_void_p))
+
+    def set_pos(self, x, rank=0):
+        x = np.ascontiguousarray(x, np.float64); assert x.shape == (self.L.rxo_natoms(self.w, rank), 3)
+        self.L.rxo_set_pos.argtypes = [C.c_void_p, C.c_int, C.c_void_p]; self.L.rxo_set_pos(self.w, rank, x.ctypes.data_as(C.c_void_p))
 
     def set_qstep(self, qstep):
         self.L.rxo_set_qstep.argtypes = [C.c_void_p, C.c_int]; self.L.rxo_set_qstep(self.w, int(qstep))

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 
 import oracle_api as oa
+import npt_reference as npt
+from npt_reference import mu_np as _mu_np, volume as _volume, hmat as _hmat
 from test_gpu_parity import _engine, _oracle, q_err, f_err, e_err, QTOL, FTOL, ETOL
 
 pytestmark = pytest.mark.gpu
@@ -26,21 +28,6 @@ def _fresh(case, mc, lat, **kw):
     e = rxmd_amd.RxmdEngine(ff, lat, **kw)
     e.set_atoms_rxff(rec)
     return e
-
-
-def _volume(lat):
-    a, b, c = lat[:3]
-    ca, cb, cg = np.cos(np.radians(lat[3:6]))
-    return a * b * c * np.sqrt(1.0 - ca * ca - cb * cb - cg * cg + 2.0 * ca * cb * cg)
-
-
-def _hmat(lat):
-    """GetBoxParams (init.F90:610-633): columns are the lattice vectors"""
-    la, lb, lc = lat[:3]
-    al, be, ga = np.radians(lat[3:6])
-    hh1 = lc * (np.cos(al) - np.cos(be) * np.cos(ga)) / np.sin(ga)
-    hh2 = lc * np.sqrt(1.0 - np.cos(al) ** 2 - np.cos(be) ** 2 - np.cos(ga) ** 2 + 2 * np.cos(al) * np.cos(be) * np.cos(ga)) / np.sin(ga)
-    return np.array([[la, lb * np.cos(ga), lc * np.cos(be)], [0.0, lb * np.sin(ga), hh1], [0.0, 0.0, hh2]])
 
 
 def _by_gid(a):
@@ -189,16 +176,6 @@ def test_barostat_off_changes_nothing():
     for k in a:
         assert np.array_equal(a[k], b[k]), k
     assert np.abs(pa - pb).max() <= 1e-12 * abs(pa[0]) and la == lb and sb["couplings"] == 0   # (energies are summed with atomics)
-
-
-def _mu_np(p6, mode, p0, rate, B, max_strain, axes=7):
-    mu = np.ones(3)
-    for k in range(3):
-        if mode == 1:
-            mu[k] = np.cbrt(1.0 - rate * (p0[0] - (p6[0] + p6[1] + p6[2]) / 3.0) / B)
-        elif (axes >> k) & 1:
-            mu[k] = np.cbrt(1.0 - rate * (p0[k] - p6[k]) / B)
-    return np.clip(mu, 1.0 - max_strain, 1.0 + max_strain)
 
 
 def _coupled_run(qeq_mode, tau, max_strain, read_every_step, nsteps=5):
@@ -363,8 +340,9 @@ def _port():
 
 def test_two_ranks_couple_to_the_same_lattice():
     """vprocs (2,1,1), two processes on one GPU over gloo.  The virial of the first FORCE summed over the two ranks is the one-rank virial and
-    the oracle's two-rank sum; 10 isotropic couplings give the same lattice on both ranks bit for bit, within 1e-12 of the one-rank run, energies
-    to 1e-9; a rank given another lattice makes set_lattice fail with RXMD_E_ARG on both"""
+    the oracle's two-rank sum; 10 isotropic couplings give the same lattice on both ranks bit for bit, and every one of them and the final
+    energies are those of the two-rank oracle under the numpy barostat (tests/npt_reference.py) started from the engine's velocities; a rank
+    given another lattice makes set_lattice fail with RXMD_E_ARG on both"""
     import torch.multiprocessing as mp
     import vc_worker
     ctx = mp.get_context("spawn")
@@ -400,3 +378,21 @@ def test_two_ranks_couple_to_the_same_lattice():
     assert np.array_equal(l0, l1)
     assert res[0]["mismatch_rc"] == -1 and res[1]["mismatch_rc"] == -1
     assert res[0]["lattice_after_mismatch"] == res[0]["lattices"][-1]
+    # Against the two-rank oracle (the one-rank comparison above stays a printed line: the two pressures legitimately differ).
+    # The engine's velocity draw is handed over explicitly; the lattice gate is derived in tests/test_gpu_variable_cell_oracle.py
+    # (k couplings x 1e-10 relative), the energies are gated at ETOL.
+    v = np.zeros((1344, 3))
+    for r in res:
+        v[np.array(r["gid0"]) - 1] = np.array(r["v0"])
+    ob = oa.Oracle(ff, lat2, ranks, vprocs=(2, 1, 1), v0=[v[g["gid"] - 1] for g in ranks], **TIGHT); ob.qeq(); ob.force()
+    assert e_err(pe0, ob.energy()) <= ETOL
+    Lf, rows = npt.berendsen_run(ob, lat2, 10, 1, 0.0, 25.0, 15.0, every=1, max_strain=0.01)
+    ob.qeq(); ob.force()
+    for k, row in enumerate(rows):
+        d = max(abs(l0[k][a] - row["new"][a]) / row["new"][a] for a in range(3))
+        dp = np.abs(np.array(res[0]["p6"][k]) - row["p6"]).max() / np.abs(row["p6"]).max()
+        print("two ranks against the two-rank oracle, coupling %d: lattice %.3e relative (gate %.0e), p6 %.3e of its largest component" % (k + 1, d, (k + 1) * 1e-10, dp))
+        assert d <= (k + 1) * 1e-10
+        assert list(l0[k][3:]) == list(row["new"][3:])
+    print("two ranks against the two-rank oracle after 10 couplings: energies %.3e (gate %.0e)" % (e_err(pe, ob.energy()), ETOL))
+    assert e_err(pe, ob.energy()) <= ETOL
