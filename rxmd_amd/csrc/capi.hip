@@ -498,7 +498,7 @@ int rxmd_hip_debug_get(rxmd_handle h, int what, double *out, int capacity) {
       case 10: n = G; if (capacity < n) throw EngineError(RXMD_E_ARG, "capacity"); pull_d(e.cc_, G, 1, 0); break;
       case 14: {   // RXMD_POISON_ALLOC: {1 if the pattern is on, the LAST entry of row 0 of the 10 A value array} -- an element no kernel writes (rows are shorter than their slot)
         n = 2; if (capacity < 2) throw EngineError(RXMD_E_ARG, "capacity");
-        out[0] = e.poison_on() ? 1.0 : 0.0;
+        out[0] = rxmd::poison_enabled() ? 1.0 : 0.0;
         RX_HIP(hipMemcpy(out + 1, e.hess + (e.S10 - 1), sizeof(double), hipMemcpyDeviceToHost));
         break;
       }
@@ -584,7 +584,7 @@ int rxmd_hip_comm_init_rccl(rxmd_handle h, const unsigned char id128[128], int r
 int rxmd_hip_set_exchange_buffers(rxmd_handle h, double *send, double *recv, long long ndoubles) {
   return guarded(h, [&](Engine &e) {
     if (!send || !recv || ndoubles < 1024) throw EngineError(RXMD_E_ARG, "bad exchange buffers");
-    if (e.xbuf_owned) { (void)hipFree(e.xbuf_send); (void)hipFree(e.xbuf_recv); }
+    e.bufs.free_group(rxmd::G_XBUF);                       // (the engine's own pair, if it had one)
     e.xbuf_send = send; e.xbuf_recv = recv; e.xbuf_doubles = static_cast<size_t>(ndoubles); e.xbuf_owned = false;
   });
 }

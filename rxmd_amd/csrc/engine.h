@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rxmd_hip.h"
@@ -150,6 +151,50 @@ constexpr int WIN_UNIT = 8;         // cell-sorted positions per window unit (8 
 constexpr int WIN_MAXUNITS = 448;   // units a group's descriptor holds: 3,584 slots = 56 KB of LDS (two workgroups per CU)
 constexpr int WIN_BMW = 2048;       // 64-bit words of the coverage map the build kernel keeps in LDS: a group's positions may span 2048 x 64 x 8 = 1 M
 
+// ---- buffers.hip: the one allocator of the library, and the table of the engine's buffers --------------------------------------------
+// Fill::Pattern: zeros, or 0xFF bytes under RXMD_POISON_ALLOC=1; Fill::Zero: the zero is part of a protocol; Fill::None: the owner writes all of it
+enum class Fill : unsigned char { None, Zero, Pattern };
+void *dev_alloc(size_t bytes, Fill fill);
+void dev_free(void *p);
+void *pinned_alloc(size_t bytes, bool coherent_mapped);   // always zeroed; coherent_mapped: a kernel stores into it and the host polls it
+void pinned_free(void *p);
+bool poison_enabled();
+template <class T> void dev_alloc(T *&p, size_t n, Fill fill) { p = static_cast<T *>(dev_alloc(n * sizeof(T), fill)); }
+template <class T> void dev_free(T *&p) { dev_free(static_cast<void *>(p)); p = nullptr; }
+
+struct Engine;
+enum class Dim : unsigned char { Fixed, NB, Rows10, List10, Cap };   // what a buffer's count scales with: nothing, NB, rows10, rows10 * S10, the capacity of its group
+enum class Refill : unsigned char { Never, Whole, Ghosts };          // RXMD_POISON_ALLOC refill before a rebuild: none, the whole buffer, elements [N, NB)
+enum class Space : unsigned char { Device, Pinned, PinnedCoherent };
+// re-allocation groups.  Those before G_ON_DEMAND exist from set-up on (Buffers::alloc_setup); the others are allocated when first needed
+enum { G_SETUP, G_BOND, G_WIN, G_CELLSTART, G_LIST10, G_PARTIALS, G_ON_DEMAND, G_CUBTMP = G_ON_DEMAND, G_FFBLOB, G_PQBLOB, G_E4B, G_SEG, G_SEG_PINNED, G_XBUF, G_DH_SERVE, G_COUNT };
+enum : unsigned { BUF_PQEQ = 1u, BUF_RESIDENT = 2u };                // exists only with PQEq ; resident state that grow_capacity carries over
+struct Buf { void **pp; size_t elem; int group; Dim dim; size_t mul, add_; Fill fill; Refill refill; unsigned flags; Space space; size_t bytes; };   // bytes: what was allocated (0: nothing of ours)
+struct Buffers {
+  std::vector<Buf> v;
+  size_t cap[G_COUNT] = {};        // capacity each group was last allocated at (Dim::Cap)
+  template <class T> void add(T *&p, int group, Dim dim, size_t mul, size_t addend, Fill fill, Refill refill, unsigned flags = 0) {
+    size_t elem = 1;               // (void *: bytes)
+    if constexpr (!std::is_void_v<T>) elem = sizeof(T);
+    add_raw(reinterpret_cast<void **>(&p), elem, group, dim, mul, addend, fill, refill, flags);
+  }
+  void add_raw(void **pp, size_t elem, int group, Dim dim, size_t mul, size_t addend, Fill fill, Refill refill, unsigned flags = 0) {
+    v.push_back(Buf{pp, elem, group, dim, mul, addend, fill, refill, flags, Space::Device, 0});
+  }
+  template <class T> void add_pinned(T *&p, int group, size_t n, bool coherent_mapped) {
+    v.push_back(Buf{reinterpret_cast<void **>(&p), sizeof(T), group, Dim::Fixed, 0, n, Fill::Zero, Refill::Never, 0u, coherent_mapped ? Space::PinnedCoherent : Space::Pinned, 0});
+  }
+  size_t count(const Buf &b, const Engine &e) const;
+  void alloc_one(Buf &b, const Engine &e); void free_one(Buf &b);
+  void alloc_setup(const Engine &e);                               // every group that exists from set-up on, at the capacities in cap[]
+  void alloc_group(const Engine &e, int group, size_t capacity = 0);   // all or nothing; capacity only for groups with a Dim::Cap entry (the caller frees the group first unless it keeps the old blocks itself)
+  void free_group(int group); void free_all();
+  void refill(const Engine &e);
+  std::vector<std::vector<char>> save_residents(const Engine &e) const;
+  void restore_residents(const std::vector<std::vector<char>> &h);
+};
+constexpr size_t EHB_DON_EXTRA = 64 * 256 + 256;   // donor list beyond one entry per row: 64 sub-lists (bonded.hip EHB_REGIONS) padded to 256
+
 struct ScaleArgs;
 struct Engine {
   const Options opt = Options::from_env();   // the environment switches of this engine (options.def), read once at create
@@ -173,7 +218,9 @@ struct Engine {
   Grid grid{};
   RefMesh rmesh{};
 
-  // ---- device memory ----
+  // ---- device memory (declared once, in Engine::declare_buffers of buffers.hip) ----
+  Buffers bufs;
+  void declare_buffers();
   DevFF dff{};
   void *ffblob = nullptr, *pqblob = nullptr;
   double *pos[3] = {}, *vel[3] = {}, *frc[3] = {}, *spos[3] = {};  // real pos, v, f ; normalised-local pos (ghost build)
@@ -233,7 +280,7 @@ struct Engine {
   hipStream_t stream = nullptr;
   // second stream for the halo exchanges that overlap with compute (multi-rank): pack / RCCL send-recv / unpack run here while
   // the main stream works on what does not need the ghosts yet; events order the two (engine.hip: on_comm_stream)
-  hipStream_t comm_stream = nullptr; hipEvent_t ev_main = nullptr, ev_comm = nullptr, ev_est = nullptr, ev_spec[2] = {nullptr, nullptr}, ev_upd[2] = {nullptr, nullptr}, ev_pass[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // ev_est: Est of a CG iteration has reached the host
+  hipStream_t comm_stream = nullptr; hipEvent_t ev_main = nullptr, ev_comm = nullptr, ev_est = nullptr, ev_pass[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // ev_est: Est of a CG iteration has reached the host
   template <class F> void on_comm_stream(F &&body) {          // body runs with `stream` == comm_stream, after everything queued on the main stream so far
     RX_HIP(hipEventRecord(ev_main, stream));
     RX_HIP(hipStreamWaitEvent(comm_stream, ev_main, 0));
@@ -273,8 +320,6 @@ struct Engine {
   // the packed type is split on the device.  Only once the engine is sized (after a first set_atoms_rxff); velocities are zeroed.
   void set_atoms_arrays(int natoms, const double *atype, const double *x, const double *y, const double *z, const double *q, const double *lexp, const double *lexv);
   int get_atoms_rxff(double *rec10, int capacity);
-  bool poison_on() const;
-  void poison_step_scratch();   // RXMD_POISON_ALLOC=1 (engine.hip): the per-step scratch holds 0xFF bytes again before every rebuild
   void build_ghosts_and_lists(bool qeq_prepass = false);   // COPYATOMS(MODE_COPY) + LINKEDLIST + NEIGHBORLIST + 10 A list/hessian, once per step
   void qeq_start_vectors();        // qs, qt, hs, ht of qeq.F90:36-63 and their cell-sorted copy (before the list sweep that uses them)
   int *rows_int = nullptr, *rows_bnd = nullptr; int n_bnd = 0; bool rows_split_pending = false;   // interior / boundary rows (multi-rank)
@@ -306,7 +351,7 @@ struct Engine {
   void derive_box_geometry();                  // the same for `box`, into the members
   long long capacity_want(const double shell_n[3]) const;   // the NB set-up would choose for a ghost shell shell_n (rxmd_config.nbuffer = 0)
   void grow_capacity(int new_nb);              // every per-atom buffer re-allocated at new_nb; the residents' state and the device scalars kept
-  void alloc_window_groups(size_t nb, size_t ng);   // ng window groups (win_groups_bound(rows10) + 1 of a grid) + rpos / g_rrow
+  void alloc_window_groups(size_t ng);   // ng window groups (win_groups_bound(rows10) + 1 of a grid) + rpos / g_rrow
   size_t cellstart_cap = 0, win_ng_cap = 0;    // what is allocated: grid.nfine + 2 ; win_groups_bound(rows10) + 1 of the grid they were sized for
   long long nsize_setup = 0;                   // the per-rank atom count set-up sized the engine for
   // Berendsen barostat (rxmd_hip_set_barostat): mode 0 off, 1 isotropic, 2 per axis; coupled behind the second half-kick of every `every`-th step

@@ -18,37 +18,6 @@ static const int NMINCELL = 4;             // reference src/module.F90:84
 static const int cptridx_[7] = {0, 0, 0, 2, 2, 4, 4};  // comm.F90:61
 static const int dinv_[7] = {0, 2, 1, 4, 3, 6, 5};     // comm.F90:60
 
-// RXMD_POISON_ALLOC=1 (diagnostic; changes nothing that is computed): every buffer starts as 0xFF bytes -- a NaN for doubles, -1 for
-// indices and counts -- instead of zeros, and the per-step scratch (ghost slots of the per-atom arrays, bonded tables, the 10 A list and its
-// window form) is filled with the pattern again before every rebuild (Engine::poison_step_scratch), so that a kernel which reads an element
-// nobody wrote this step shows as a NaN / an index trap instead of silently using a stale or zero value.  The reference's own allocator does not
-// clear (module.F90:732-744); what it clears explicitly -- ccbnd, cdbnd, f, PE per FORCE call (pot.F90:20-26), spos and qtfp/qtfv at
-// allocation (init.F90:117-131) -- the kernels here clear too.  Buffers whose ZERO is part of a protocol (arrival counters, error words,
-// device scalars) are allocated with dzalloc.
-static const Options g_opt = Options::from_env();      // (allocation helpers are free functions: the library-wide copy of the switches)
-static const bool g_poison = g_opt.poison_alloc;
-#ifdef RXMD_EXPERIMENTS
-// RXMD_CONTIG_ALLOC=<bytes>: buffers of at most that many bytes (0: every buffer) come from hipExtMallocWithFlags(hipDeviceMallocContiguous) -- the
-// configuration that failed 15 unrelated tests in round 3 (NOTES.md 3); with RXMD_POISON_ALLOC=1 a read of stale memory shows as a NaN
-static const long long g_contig = g_opt.contig_alloc;
-#endif
-template <class T>
-static void dmalloc(T *&p, size_t n) {
-  const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-#ifdef RXMD_EXPERIMENTS
-  if (g_contig == 0 || (g_contig > 0 && bytes <= static_cast<size_t>(g_contig))) RX_HIP(hipExtMallocWithFlags(reinterpret_cast<void **>(&p), bytes, hipDeviceMallocContiguous));
-  else
-#endif
-  RX_HIP(hipMalloc(reinterpret_cast<void **>(&p), bytes));
-  RX_HIP(hipMemset(p, g_poison ? 0xFF : 0, bytes));
-}
-template <class T>
-static void dzalloc(T *&p, size_t n) {
-  RX_HIP(hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(n, 1) * sizeof(T)));
-  RX_HIP(hipMemset(p, 0, std::max<size_t>(n, 1) * sizeof(T)));
-}
-template <class T>
-static void dfree(T *&p) { if (p) { (void)hipFree(p); p = nullptr; } }
 
 static void make_box(Box &b, const double lat[6], const int vprocs[3], const int vID[3]) {
   // GetBoxParams (reference src/init.F90:610-633)
@@ -86,6 +55,7 @@ static bool lattice_spans_box(const double *L) {
 static bool lattice_orthorhombic(const double *L) { return std::fabs(L[3] - 90.0) < 1e-9 && std::fabs(L[4] - 90.0) < 1e-9 && std::fabs(L[5] - 90.0) < 1e-9; }   // (the test of grid.ortho)
 
 Engine::Engine(const rxmd_config &c) : cfg(c) {
+  declare_buffers();
   if (!c.ffield_path) throw EngineError(RXMD_E_ARG, "ffield_path is NULL");
   ffield_path = c.ffield_path;
   cfg.ffield_path = ffield_path.c_str();
@@ -148,8 +118,6 @@ Engine::Engine(const rxmd_config &c) : cfg(c) {
   RX_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming)); RX_HIP(hipEventCreateWithFlags(&ev_bond, hipEventDisableTiming));
   RX_HIP(hipEventCreateWithFlags(&ev_main, hipEventDisableTiming)); RX_HIP(hipEventCreateWithFlags(&ev_comm, hipEventDisableTiming));
   RX_HIP(hipEventCreateWithFlags(&ev_est, hipEventDisableTiming));
-  RX_HIP(hipEventCreateWithFlags(&ev_spec[0], hipEventDisableTiming)); RX_HIP(hipEventCreateWithFlags(&ev_spec[1], hipEventDisableTiming));
-  RX_HIP(hipEventCreateWithFlags(&ev_upd[0], hipEventDisableTiming)); RX_HIP(hipEventCreateWithFlags(&ev_upd[1], hipEventDisableTiming));
   for (auto &pr : ev_pass) for (auto &e2 : pr) RX_HIP(hipEventCreate(&e2));
   for (auto &e : ev) RX_HIP(hipEventCreate(&e));
 }
@@ -165,8 +133,6 @@ Engine::~Engine() {
   if (ev_main) (void)hipEventDestroy(ev_main);
   if (ev_comm) (void)hipEventDestroy(ev_comm);
   if (ev_est) (void)hipEventDestroy(ev_est);
-  for (auto &e2 : ev_spec) if (e2) (void)hipEventDestroy(e2);
-  for (auto &e2 : ev_upd) if (e2) (void)hipEventDestroy(e2);
   for (auto &pr : ev_pass) for (auto &e2 : pr) if (e2) (void)hipEventDestroy(e2);
   if (comm_stream && comm_stream != stream) (void)hipStreamDestroy(comm_stream);
   if (stream) (void)hipStreamDestroy(stream);
@@ -183,12 +149,12 @@ void Engine::allreduce_host(double *buf, int n) {
   }
   if (nccl) {
     double *d = nullptr;
-    RX_HIP(hipMalloc(reinterpret_cast<void **>(&d), sizeof(double) * n));
+    dev_alloc(d, n, Fill::None);
     RX_HIP(hipMemcpyAsync(d, buf, sizeof(double) * n, hipMemcpyHostToDevice, stream));
     rccl_allreduce_dev(d, n);
     RX_HIP(hipMemcpyAsync(buf, d, sizeof(double) * n, hipMemcpyDeviceToHost, stream));
     sync_stream();
-    (void)hipFree(d);
+    dev_free(d);
     return;
   }
   if (!has_comm || !comm.allreduce_sum) throw EngineError(RXMD_E_COMM, "vprocs > 1 needs a transport: call rxmd_hip_set_comm or rxmd_hip_comm_init_rccl first");
@@ -351,8 +317,7 @@ void Engine::upload_ff() {
                          nb.size() * sizeof(DevNBTab), ff.tblQEq.size() * 8, tq2.size() * sizeof(double2)};
   const void *src[12] = {a.data(), b.data(), an.data(), to.data(), hb.data(), ff.inxn2.data(), ff.inxn3.data(), ff.inxn3hb.data(), inxn4x.data(), nb.data(), ff.tblQEq.data(), tq2.data()};
   for (int i = 0; i < 12; ++i) { off[i] = tot; tot += al(sz[i]); }
-  if (ffblob) { (void)hipFree(ffblob); ffblob = nullptr; }
-  RX_HIP(hipMalloc(&ffblob, tot));
+  bufs.free_group(G_FFBLOB); bufs.alloc_group(*this, G_FFBLOB, tot);
   for (int i = 0; i < 12; ++i) RX_HIP(hipMemcpy(static_cast<char *>(ffblob) + off[i], src[i], sz[i], hipMemcpyHostToDevice));
   char *base = static_cast<char *>(ffblob);
   dff.nso = ff.nso; dff.n1 = n1; dff.nboty = ff.nboty; dff.ntoty = ff.ntoty; dff.nvaty = ff.nvaty;
@@ -376,8 +341,7 @@ void Engine::upload_ff() {
         if (ff.inxn3hb[(t * n1 + 2) * n1 + k] != 0) ehb_donor_types |= 1u << t;
   if (ff.pqeq) {
     const size_t b0 = al(zk.size() * 8), b1 = al(ff.inxnpq.size() * 4), bt = al(pt[0].size() * sizeof(double4));
-    if (pqblob) { (void)hipFree(pqblob); pqblob = nullptr; }
-    RX_HIP(hipMalloc(&pqblob, b0 + b1 + 3 * bt));
+    bufs.free_group(G_PQBLOB); bufs.alloc_group(*this, G_PQBLOB, b0 + b1 + 3 * bt);
     char *pb = static_cast<char *>(pqblob);
     RX_HIP(hipMemcpy(pb, zk.data(), zk.size() * 8, hipMemcpyHostToDevice));
     RX_HIP(hipMemcpy(pb + b0, ff.inxnpq.data(), ff.inxnpq.size() * 4, hipMemcpyHostToDevice));
@@ -389,102 +353,39 @@ void Engine::upload_ff() {
 }
 
 void Engine::alloc_device() {
-  const size_t nb = NB, ns = static_cast<size_t>(NB) * 32;      // staging of the bonded sweep: one 128-byte line of 32 slots per atom (lists.hip, BL_STRIDE; MAXNB <= 31)
-  for (int a = 0; a < 3; ++a) { dmalloc(pos[a], nb); dmalloc(vel[a], nb); dmalloc(frc[a], nb); dmalloc(spos[a], nb); }
-  dmalloc(q, nb); dmalloc(qsfp, nb); dmalloc(qsfv, nb); dmalloc(type, nb); dmalloc(gid, nb);
-  if (ff.pqeq) {
-    for (int a = 0; a < 3; ++a) dmalloc(shl[a], nb);
-    dmalloc(sorted_shl, nb); dmalloc(hsc, static_cast<size_t>(rows10) * S10); dmalloc(pqrow, static_cast<size_t>(rows10));
-  }
-  dmalloc(qst, nb); dmalloc(hst, nb); dmalloc(gst, nb); dmalloc(hst2, nb); dzalloc(tickets, 16);
-  { dmalloc(sall, static_cast<size_t>(rows10)); dmalloc(sgh, static_cast<size_t>(rows10)); dmalloc(wall, static_cast<size_t>(rows10)); dmalloc(wgh, static_cast<size_t>(rows10)); }
-  dmalloc(gsrc, nb); dmalloc(groot, nb); dmalloc(gowner, nb); dmalloc(dh_ghost, nb); dmalloc(dh_keys, nb); dmalloc(dh_keys2, nb); dmalloc(dh_vals, nb); dmalloc(dh_off, 1100); dmalloc(sendidx, nb); dmalloc(rootperm, nb); dmalloc(invpos, nb); dmalloc(xs, nb); for (int a = 0; a < 3; ++a) { dmalloc(fnb[a], nb); dmalloc(fsort[a], nb); }
+  const size_t nb = NB;
+  // the capacities of the groups that exist from set-up on; which buffers they size, and how, is the table's business (buffers.hip)
   cellstart_cap = static_cast<size_t>(grid.nfine) + 2;
-  dmalloc(cellid, nb); dmalloc(cellid_sorted, nb); dmalloc(perm, nb); dmalloc(perm_in, nb); dmalloc(cellstart, cellstart_cap);
-  dmalloc(sorted_xyzi, nb); dmalloc(sorted_type, nb); dmalloc(flags, nb + 1); dmalloc(scanout, nb + 1); dmalloc(flags2, nb + 1); dmalloc(scanout2, nb + 1);
-  dmalloc(nbr_sm, ns); dmalloc(nbrcnt, nb + 1); dmalloc(boff, nb + 2);
-  {   // 5.3 bonds per RDX atom, ~16 in SiC: 12 per atom slot to start with, grown when a build needs more (build_ghosts_and_lists).
-      // RXMD_BOND_CAP=<bonds>: start smaller (the tests walk the growth path with it; a capacity, not a result)
-    size_t cap = std::min<size_t>(ns, nb * 12);
-    if (opt.bond_cap > 0) cap = static_cast<size_t>(opt.bond_cap);
-    alloc_bond_tables(cap);
-  }
-  ehb_don_cap = static_cast<size_t>(rows10) + 64 * 256 + 256; dmalloc(ehb_don, ehb_don_cap); dzalloc(ehb_cnt, 72);   // 64 sub-lists (bonded.hip EHB_REGIONS) + debug words
-  dmalloc(ecoef, 6 * nb); dmalloc(deltap, nb); dmalloc(delta, nb); dmalloc(nlp, nb); dmalloc(dDlp, nb); dmalloc(deltalp, nb); dmalloc(cds, nb); dmalloc(cd, nb); dmalloc(cc_, nb);
-  dmalloc(nb10, static_cast<size_t>(rows10) * S10);
-  dmalloc(rows_int, static_cast<size_t>(rows10)); dmalloc(rows_bnd, static_cast<size_t>(rows10));
-  dmalloc(hess, static_cast<size_t>(rows10) * S10); dmalloc(n10, static_cast<size_t>(rows10));
-  alloc_window_groups(nb, win_groups_bound(rows10) + 1);
-  dmalloc(sl10, static_cast<size_t>(rows10) * S10);
+  // 5.3 bonds per RDX atom, ~16 in SiC: 12 per atom slot to start with, grown when a build needs more (build_ghosts_and_lists).
+  // RXMD_BOND_CAP=<bonds>: start smaller (the tests walk the growth path with it; a capacity, not a result)
+  bcap = std::max<size_t>(opt.bond_cap > 0 ? static_cast<size_t>(opt.bond_cap) : nb * 12, 1024);
+  win_ng_cap = win_groups_bound(rows10) + 1;
+  ehb_don_cap = static_cast<size_t>(rows10) + EHB_DON_EXTRA;
   partials_cap = std::max<size_t>(size_t(1) << 16, 4 * static_cast<size_t>(rows10) + 16384);   // up to one workgroup (4 partial sums) per row
-  dmalloc(partials, partials_cap + 1024); dzalloc(scal, SCAL_N);   // + the 128 x 4 first-level sums of k_reduce_fused, behind the per-workgroup partials at a fixed offset
-  RX_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_scal), 320 * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));   // coherent: the update kernel's tail stores the CG snapshot into it and the host polls it      // [0,64): as before; [64,192): the two slots of the run-ahead CG loop (qeq.hip); [192,288): the per-type sums of a host transport
-  // Pinned memory comes back from the allocator as the last owner left it, and a process may hold several engines one after another: a stale
-  // sequence word of an earlier engine's CG snapshot could satisfy wait_snapshot's poll.  Zeroed where it is allocated (set-up and grow_capacity
-  // both come through here).  Which block the allocator hands out is its choice, so no test can pin this.
-  std::memset(h_scal, 0, 320 * sizeof(double));
-  dzalloc(tsum, 128); { double *sa_ = nullptr; dzalloc(sa_, 32); sargs = reinterpret_cast<ScaleArgs *>(sa_); }
-  dzalloc(d_err, 16);
-  RX_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_err), 32 * sizeof(int)));
-  std::memset(h_err, 0, 32 * sizeof(int));
+  bufs.cap[G_CELLSTART] = cellstart_cap; bufs.cap[G_BOND] = bcap; bufs.cap[G_WIN] = win_ng_cap; bufs.cap[G_PARTIALS] = partials_cap;
+  bufs.alloc_setup(*this);
   h_cnt = h_err + 16;
   // hipcub scratch sized for the largest scan / sort we issue
   size_t b1 = 0, b2 = 0;
   hipcub::DeviceScan::ExclusiveSum(nullptr, b1, flags, scanout, NB + 1, stream);
   hipcub::DeviceRadixSort::SortPairs(nullptr, b2, cellid, cellid_sorted, perm_in, perm, NB, 0, 32, stream);
   cubtmp_bytes = std::max(b1, b2) + 256;
-  RX_HIP(hipMalloc(&cubtmp, cubtmp_bytes));
+  bufs.alloc_group(*this, G_CUBTMP, cubtmp_bytes);
 }
 
-// groups never straddle a cell column of the grid: up to one short group per column (win_groups_bound)
-void Engine::alloc_window_groups(size_t nb, size_t ng) {
-  win_ng_cap = ng;
-  for (double2 **pp : {&r_qst, &r_hst, &r_hst2, &r_gst, &r_sall, &r_sgh, &r_wall, &r_wgh}) dmalloc(*pp, ng * WIN_ROWS);
-  dmalloc(r_type, ng * WIN_ROWS); dmalloc(r_n10, ng * WIN_ROWS); dmalloc(r_xpos, ng * WIN_ROWS); dmalloc(rpos, nb); dmalloc(g_rrow, nb);
-  dmalloc(rows_sorted, ng * WIN_ROWS); dmalloc(rowcols, ng * WIN_ROWS * 64); dmalloc(grp_base, ng * 32); dmalloc(win_flag, ng + 1); dmalloc(win_k, ng * WIN_MAXUNITS); dmalloc(win_cnt, ng); dmalloc(win_gint, ng); dmalloc(win_gbnd, ng);
-}
-
-void Engine::alloc_bond_tables(size_t cap) {
-  bcap = std::max<size_t>(cap, 1024);
-  dmalloc(nbr, bcap); dmalloc(brev, bcap); dmalloc(bown, bcap); dmalloc(btype, bcap);
-  for (double **t : {&bo0, &bo1, &bo2, &bo3, &dln2, &dln3, &dBOp, &A0, &A1, &A2, &A3, &cf1, &cf2, &cf3, &cdn, &fnx, &fny, &fnz, &etor, &econ, &epen, &ecoa, &bt1, &bt2, &bt3}) dmalloc(*t, bcap);
-}
+void Engine::alloc_window_groups(size_t ng) { win_ng_cap = ng; bufs.alloc_group(*this, G_WIN, ng); }
+void Engine::alloc_bond_tables(size_t cap) { bcap = std::max<size_t>(cap, 1024); bufs.alloc_group(*this, G_BOND, bcap); }
 void Engine::alloc_e4b_delivery(size_t entries) {
-  dfree(e4b_t); dfree(e4b_flag);
+  bufs.free_group(G_E4B);
   e4b_cap = (std::max<size_t>(entries, 1024) + 3) & ~static_cast<size_t>(3);
-  dmalloc(e4b_t, e4b_cap); dzalloc(e4b_flag, e4b_cap);
+  bufs.alloc_group(*this, G_E4B, e4b_cap);
   e4b_dirty = false;
 }
-void Engine::free_bond_tables() {
-  dfree(nbr); dfree(brev); dfree(bown); dfree(btype);
-  for (double **t : {&bo0, &bo1, &bo2, &bo3, &dln2, &dln3, &dBOp, &A0, &A1, &A2, &A3, &cf1, &cf2, &cf3, &cdn, &fnx, &fny, &fnz, &etor, &econ, &epen, &ecoa, &bt1, &bt2, &bt3}) dfree(*t);
-  bcap = 0;
-}
+void Engine::free_bond_tables() { bufs.free_group(G_BOND); bcap = 0; }
 
 void Engine::free_device() {
-  for (int a = 0; a < 3; ++a) { dfree(flags2); dfree(scanout2); dfree(pos[a]); dfree(vel[a]); dfree(frc[a]); dfree(spos[a]); }
-  for (int a = 0; a < 3; ++a) dfree(shl[a]);
-  dfree(sorted_shl); dfree(hsc); dfree(pqrow);
-  if (pqblob) { (void)hipFree(pqblob); pqblob = nullptr; }
-  dfree(q); dfree(qsfp); dfree(qsfv); dfree(type); dfree(gid); dfree(qst); dfree(hst); dfree(gst); dfree(hst2); dfree(tickets); dfree(sall); dfree(sgh); dfree(wall); dfree(wgh);
-  dfree(gowner); dfree(dh_ghost); dfree(dh_keys); dfree(dh_keys2); dfree(dh_vals); dfree(dh_off); dfree(dh_serve);
-  dfree(gsrc); dfree(groot); dfree(sendidx); dfree(rootperm); dfree(invpos); dfree(xs); for (int a = 0; a < 3; ++a) { dfree(fnb[a]); dfree(fsort[a]); } dfree(cellid); dfree(cellid_sorted); dfree(perm); dfree(perm_in); dfree(cellstart);
-  dfree(sorted_xyzi); dfree(sorted_type); dfree(flags); dfree(scanout); dfree(nbr_sm); dfree(nbrcnt); dfree(boff);
-  free_bond_tables();
-  dfree(ehb_don); dfree(ehb_cnt); dfree(e4b_t); dfree(e4b_flag); e4b_cap = 0;
-  dfree(ecoef); dfree(deltap); dfree(delta); dfree(nlp); dfree(dDlp); dfree(deltalp); dfree(cds); dfree(cd); dfree(cc_);
-  for (double2 **pp : {&r_qst, &r_hst, &r_hst2, &r_gst, &r_sall, &r_sgh, &r_wall, &r_wgh}) dfree(*pp);
-  dfree(r_type); dfree(r_n10); dfree(r_xpos); dfree(rpos); dfree(g_rrow);
-  dfree(rows_int); dfree(rows_bnd); dfree(rows_sorted); dfree(rowcols); dfree(grp_base); dfree(win_flag); dfree(win_k); dfree(win_cnt); dfree(win_gint); dfree(win_gbnd); dfree(sl10);
-  dfree(nb10); dfree(hess); dfree(n10); dfree(partials); dfree(scal); dfree(d_err); dfree(tsum); { double *sa_ = reinterpret_cast<double *>(sargs); dfree(sa_); sargs = nullptr; }
-  if (xbuf_owned) { dfree(xbuf_send); dfree(xbuf_recv); }
-  if (h_scal) { (void)hipHostFree(h_scal); h_scal = nullptr; }
-  if (h_err) { (void)hipHostFree(h_err); h_err = nullptr; }
-  dfree(seg_cnt); dfree(seg_tot); dfree(seg_code_); seg_blocks_cap = 0;
-  if (h_seg) { (void)hipHostFree(h_seg); h_seg = nullptr; }
-  if (h_pub) { (void)hipHostFree(h_pub); h_pub = nullptr; }
-  if (cubtmp) { (void)hipFree(cubtmp); cubtmp = nullptr; }
-  if (ffblob) { (void)hipFree(ffblob); ffblob = nullptr; }
+  bufs.free_all();
+  bcap = 0; e4b_cap = 0; seg_blocks_cap = 0;
 }
 
 // ReadBIN (reference src/fileio.F90:528-552): records -> real coordinates, split atype
@@ -979,11 +880,10 @@ void Engine::migrate_fused() {
 
 void Engine::ensure_seg_buffers(int nbk) {
   if (nbk <= seg_blocks_cap) return;
-  dfree(seg_cnt); dfree(seg_tot); dfree(seg_code_);
+  bufs.free_group(G_SEG);
   seg_blocks_cap = nbk + nbk / 4 + 16;
-  dmalloc(seg_cnt, static_cast<size_t>(27) * seg_blocks_cap); dzalloc(seg_tot, 32); dmalloc(seg_code_, static_cast<size_t>(seg_blocks_cap) * 256);   // (one face code per RESIDENT: sized with the workgroup count, not with the NB of the day)
-  if (!h_seg) RX_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_seg), 32 * sizeof(int)));
-  if (!h_pub) { RX_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_pub), 32 * sizeof(unsigned long long), hipHostMallocCoherent | hipHostMallocMapped)); for (int k = 0; k < 32; ++k) h_pub[k] = 0ull; }
+  bufs.alloc_group(*this, G_SEG, static_cast<size_t>(seg_blocks_cap));
+  if (!h_seg) bufs.alloc_group(*this, G_SEG_PINNED);
 }
 
 void Engine::halo_refresh(double2 *v2, double *v1) {
@@ -1056,9 +956,9 @@ size_t Engine::migrate_xbuf_doubles(size_t from_send_count) const {
 void Engine::ensure_xbuf(size_t doubles) {
   if (doubles <= xbuf_doubles) return;
   if (!xbuf_owned && xbuf_doubles > 0) throw EngineError(RXMD_E_COMM, "host-supplied exchange buffers are too small");
-  dfree(xbuf_send); dfree(xbuf_recv);
+  bufs.free_group(G_XBUF);
   xbuf_doubles = doubles + doubles / 4 + 4096;
-  dmalloc(xbuf_send, xbuf_doubles); dmalloc(xbuf_recv, xbuf_doubles);
+  bufs.alloc_group(*this, G_XBUF, xbuf_doubles);
   xbuf_owned = true;
 }
 
@@ -1066,13 +966,13 @@ void Engine::ensure_xbuf(size_t doubles) {
 // sized them from its send count only, as the migration does, needs no worst case); host-supplied buffers cannot grow
 void Engine::grow_xbuf_keep_send(size_t need, size_t keep) {
   if (!xbuf_owned) throw EngineError(RXMD_E_NBUFFER, "incoming message larger than the host-supplied exchange buffers");
-  double *ns = nullptr, *nr = nullptr;
+  double *old_send = xbuf_send, *old_recv = xbuf_recv;            // (the old pair outlives the allocation of the new one: the table takes the new blocks over)
   const size_t cap = need + need / 4 + 4096;
-  dmalloc(ns, cap); dmalloc(nr, cap);
-  if (keep > 0) RX_HIP(hipMemcpyAsync(ns, xbuf_send, sizeof(double) * keep, hipMemcpyDeviceToDevice, stream));
+  bufs.alloc_group(*this, G_XBUF, cap);                         // (throws with the old pair and xbuf_doubles untouched)
+  xbuf_doubles = cap;
+  if (keep > 0) RX_HIP(hipMemcpyAsync(xbuf_send, old_send, sizeof(double) * keep, hipMemcpyDeviceToDevice, stream));
   sync_stream();
-  dfree(xbuf_send); dfree(xbuf_recv);
-  xbuf_send = ns; xbuf_recv = nr; xbuf_doubles = cap;
+  dev_free(old_send); dev_free(old_recv);
 }
 
 long long Engine::exchange_stage(int d, bool reverse, long long nsend, long long known_nrecv) {
@@ -1277,7 +1177,7 @@ void Engine::direct_halo_setup() {
   for (int p = 0; p < np; ++p) dh_serve_off[p + 1] = dh_serve_off[p] + static_cast<long long>(table[static_cast<size_t>(p) * np + me]);
   const long long nserve = dh_serve_off[np];
   ensure_xbuf(static_cast<size_t>(std::max<long long>(std::max<long long>(ng, nserve), 1)) * 3);      // up to three components per atom (PQEq shells)
-  if (nserve > dh_serve_cap) { dfree(dh_serve); dh_serve_cap = static_cast<int>(nserve + nserve / 4 + 1024); dmalloc(dh_serve, dh_serve_cap); }
+  if (nserve > dh_serve_cap) { bufs.free_group(G_DH_SERVE); dh_serve_cap = static_cast<int>(nserve + nserve / 4 + 1024); bufs.alloc_group(*this, G_DH_SERVE, static_cast<size_t>(dh_serve_cap)); }
   if (ng > 0) k_dh_requests<<<nblk(ng, 256), 256, 0, stream>>>(ng, dh_ghost, gowner, xbuf_send);
   exchange_many(dh_need_off, dh_serve_off, 1);                                   // my requests out, the other ranks' requests in
   if (nserve > 0) k_dh_to_int<<<nblk(nserve, 256), 256, 0, stream>>>(static_cast<int>(nserve), xbuf_recv, dh_serve, N, d_err);
@@ -1593,39 +1493,10 @@ void Engine::sorted_copy(const double2 *v) {
   k_sorted_vec<<<nblk(G, 256), 256, 0, stream>>>(G, rootperm, v, xs);
 }
 
-bool Engine::poison_on() const { return g_poison; }
-// RXMD_POISON_ALLOC: what a step rebuilds from scratch holds the pattern again before the rebuild
-void Engine::poison_step_scratch() {
-  if (!g_poison) return;
-  auto fill = [&](void *p, size_t off_bytes, size_t bytes) { if (p && bytes) RX_HIP(hipMemsetAsync(static_cast<char *>(p) + off_bytes, 0xFF, bytes, stream)); };
-  const size_t nb = NB, ng = nb - N, ns = nb * 32, nl = static_cast<size_t>(rows10) * S10;
-  for (int a = 0; a < 3; ++a) { fill(pos[a], sizeof(double) * N, sizeof(double) * ng); fill(spos[a], sizeof(double) * N, sizeof(double) * ng); fill(frc[a], sizeof(double) * N, sizeof(double) * ng); }
-  fill(q, sizeof(double) * N, sizeof(double) * ng); fill(type, sizeof(int) * N, sizeof(int) * ng); fill(gid, sizeof(long long) * N, sizeof(long long) * ng);
-  fill(gsrc, 0, sizeof(int) * nb); fill(groot, 0, sizeof(int) * nb); fill(rootperm, 0, sizeof(int) * nb); fill(invpos, 0, sizeof(int) * nb); fill(xs, 0, sizeof(double2) * nb);
-  fill(cellid, 0, sizeof(int) * nb); fill(cellid_sorted, 0, sizeof(int) * nb); fill(perm, 0, sizeof(int) * nb); fill(perm_in, 0, sizeof(int) * nb);
-  fill(cellstart, 0, sizeof(int) * cellstart_cap); fill(sorted_xyzi, 0, sizeof(double4) * nb); fill(sorted_type, 0, nb);
-  if (ff.pqeq) { fill(sorted_shl, 0, sizeof(double4) * nb); fill(hsc, 0, sizeof(double) * nl); fill(pqrow, 0, sizeof(double4) * rows10); for (int a = 0; a < 3; ++a) fill(shl[a], sizeof(double) * N, sizeof(double) * ng); }
-  fill(nbr_sm, 0, sizeof(int) * ns); fill(nbrcnt, 0, sizeof(int) * (nb + 1)); fill(boff, 0, sizeof(int) * (nb + 2));
-  fill(nbr, 0, sizeof(int) * bcap); fill(brev, 0, sizeof(int) * bcap); fill(bown, 0, sizeof(int) * bcap); fill(btype, 0, bcap);
-  for (double *t : {bo0, bo1, bo2, bo3, dln2, dln3, dBOp, A0, A1, A2, A3, cf1, cf2, cf3, cdn, fnx, fny, fnz, etor, econ, epen, ecoa, bt1, bt2, bt3}) fill(t, 0, sizeof(double) * bcap);
-  fill(ecoef, 0, sizeof(double) * 6 * nb); fill(ehb_don, 0, sizeof(int2) * ehb_don_cap);
-  for (double *t : {deltap, delta, nlp, dDlp, deltalp, cds, cd, cc_}) fill(t, 0, sizeof(double) * nb);
-  fill(nb10, 0, sizeof(int) * nl); fill(hess, 0, sizeof(double) * nl); fill(sl10, 0, sizeof(unsigned short) * nl); fill(n10, 0, sizeof(int) * rows10);
-  fill(rows_int, 0, sizeof(int) * rows10); fill(rows_bnd, 0, sizeof(int) * rows10);
-  { const size_t ngr = win_ng_cap;                 // (the sizes allocated: set_lattice re-allocates these when the grid outgrows them)
-    fill(rows_sorted, 0, sizeof(int) * ngr * WIN_ROWS); fill(rowcols, 0, sizeof(int) * ngr * WIN_ROWS * 64); fill(grp_base, 0, sizeof(int) * ngr * 32); fill(win_flag, 0, sizeof(int) * (ngr + 1)); fill(win_k, 0, sizeof(int) * ngr * WIN_MAXUNITS); fill(win_cnt, 0, sizeof(int) * ngr);
-    fill(win_gint, 0, sizeof(int) * ngr); fill(win_gbnd, 0, sizeof(int) * ngr); }
-  fill(sall, 0, sizeof(double2) * rows10); fill(sgh, 0, sizeof(double2) * rows10); fill(wall, 0, sizeof(double2) * rows10); fill(wgh, 0, sizeof(double2) * rows10);
-  fill(partials, 0, sizeof(double) * (partials_cap + 1024));
-  fill(flags, 0, sizeof(int) * (nb + 1)); fill(scanout, 0, sizeof(int) * (nb + 1)); fill(flags2, 0, sizeof(int) * (nb + 1)); fill(scanout2, 0, sizeof(int) * (nb + 1));
-  for (double2 *t : {qst, hst, gst, hst2}) fill(t, sizeof(double2) * N, sizeof(double2) * ng);
-  if (xbuf_owned) { fill(xbuf_send, 0, sizeof(double) * xbuf_doubles); fill(xbuf_recv, 0, sizeof(double) * xbuf_doubles); }
-}
-
 void Engine::build_ghosts_and_lists(bool qeq_prepass) {
   if (!atoms_set) throw EngineError(RXMD_E_STATE, "atoms were never set");
   const KtPair t_lists = outer_begin(&st.ms_lists);   // (an event pair read at a later host wait: no wait of its own)
-  poison_step_scratch();
+  bufs.refill(*this);                               // (RXMD_POISON_ALLOC only)
   { const bool kt = kt_begin(&st.ms_ghost_build); ghost_build(); kt_end(kt); }
   bin_cells();
   build_prologue(3);
@@ -1658,9 +1529,7 @@ void Engine::build_ghosts_and_lists(bool qeq_prepass) {
     if (er.code != RXMD_E_MAXNEIGHBS10 || cfg.maxneighbs10 > 0) throw;
     const int need = h_err[1];
     S10 = (static_cast<int>(need * 1.1) + 64 + 63) / 64 * 64;
-    const size_t n = static_cast<size_t>(rows10) * S10;
-    dfree(nb10); dfree(hess); dfree(sl10); dmalloc(nb10, n); dmalloc(hess, n); dmalloc(sl10, n);
-    if (ff.pqeq) { dfree(hsc); dmalloc(hsc, n); }
+    bufs.free_group(G_LIST10); bufs.alloc_group(*this, G_LIST10);   // (sized by rows10 * S10)
     st.n10_stride = S10;
     list10_retry = true;
     try { build_list10(); } catch (...) { list10_retry = false; throw; }
@@ -1754,13 +1623,8 @@ void Engine::apply_lattice(const double lat[6]) {
     // buffers sized by the grid: cellstart (cells x z-slices) and the window groups (one short group per grid column at most)
     const size_t need_cs = static_cast<size_t>(g.grid.nfine) + 2, need_ng = win_groups_bound_for(g.grid, rows10) + 1;
     if (need_cs > cellstart_cap || need_ng > win_ng_cap) sync_stream();
-    if (need_cs > cellstart_cap) { dfree(cellstart); dmalloc(cellstart, need_cs); cellstart_cap = need_cs; }
-    if (need_ng > win_ng_cap) {
-      for (double2 **pp : {&r_qst, &r_hst, &r_hst2, &r_gst, &r_sall, &r_sgh, &r_wall, &r_wgh}) dfree(*pp);
-      dfree(r_type); dfree(r_n10); dfree(r_xpos); dfree(rpos); dfree(g_rrow);
-      dfree(rows_sorted); dfree(rowcols); dfree(grp_base); dfree(win_flag); dfree(win_k); dfree(win_cnt); dfree(win_gint); dfree(win_gbnd);
-      alloc_window_groups(static_cast<size_t>(NB), need_ng);
-    }
+    if (need_cs > cellstart_cap) { bufs.free_group(G_CELLSTART); cellstart_cap = need_cs; bufs.alloc_group(*this, G_CELLSTART, need_cs); }
+    if (need_ng > win_ng_cap) { bufs.free_group(G_WIN); alloc_window_groups(need_ng); }
   }
   if (atoms_set && N > 0) {
     Mat3 M;
@@ -1786,30 +1650,14 @@ void Engine::apply_lattice(const double lat[6]) {
 void Engine::grow_capacity(int new_nb) {
   if (new_nb >= (1 << NB10_IDX_BITS)) throw EngineError(RXMD_E_NBUFFER, "more than 2^26 atoms+ghosts per GPU do not fit the packed 10 A list entry");
   RX_HIP(hipDeviceSynchronize());                  // (every stream of the engine: the bonded chain and the halo stream included)
-  const size_t n = static_cast<size_t>(N);
-  auto dbl_arrays = [&]() {
-    std::vector<double *> v = {pos[0], pos[1], pos[2], vel[0], vel[1], vel[2], frc[0], frc[1], frc[2], q, qsfp, qsfv};
-    if (ff.pqeq) for (int a = 0; a < 3; ++a) v.push_back(shl[a]);
-    return v;
-  };
-  auto vec_arrays = [&]() { return std::vector<double2 *>{qst, hst, gst}; };
-  std::vector<std::vector<double>> hd;
-  for (double *p : dbl_arrays()) { hd.emplace_back(n); if (n) RX_HIP(hipMemcpy(hd.back().data(), p, sizeof(double) * n, hipMemcpyDeviceToHost)); }
-  std::vector<std::vector<double2>> hv;
-  for (double2 *p : vec_arrays()) { hv.emplace_back(n); if (n) RX_HIP(hipMemcpy(hv.back().data(), p, sizeof(double2) * n, hipMemcpyDeviceToHost)); }
-  std::vector<int> ht(n); std::vector<long long> hg(n); std::vector<double> hs(SCAL_N);
-  if (n) { RX_HIP(hipMemcpy(ht.data(), type, sizeof(int) * n, hipMemcpyDeviceToHost)); RX_HIP(hipMemcpy(hg.data(), gid, sizeof(long long) * n, hipMemcpyDeviceToHost)); }
-  RX_HIP(hipMemcpy(hs.data(), scal, sizeof(double) * SCAL_N, hipMemcpyDeviceToHost));   // CG state, energies, stress accumulators
+  const auto kept = bufs.save_residents(*this);    // the first N elements of the resident arrays; the scalar block: CG state, energies, stress accumulators
   free_device();
   if (xbuf_owned) xbuf_doubles = 0;                // (host-supplied exchange buffers are the host's and stay)
   dh_serve_cap = 0; dh_ready = false; rows_live = false; win_valid = false;
   NB = new_nb;
   alloc_device();
   upload_ff();
-  { const auto d = dbl_arrays(); for (size_t k = 0; k < d.size(); ++k) if (n) RX_HIP(hipMemcpy(d[k], hd[k].data(), sizeof(double) * n, hipMemcpyHostToDevice)); }
-  { const auto d = vec_arrays(); for (size_t k = 0; k < d.size(); ++k) if (n) RX_HIP(hipMemcpy(d[k], hv[k].data(), sizeof(double2) * n, hipMemcpyHostToDevice)); }
-  if (n) { RX_HIP(hipMemcpy(type, ht.data(), sizeof(int) * n, hipMemcpyHostToDevice)); RX_HIP(hipMemcpy(gid, hg.data(), sizeof(long long) * n, hipMemcpyHostToDevice)); }
-  RX_HIP(hipMemcpy(scal, hs.data(), sizeof(double) * SCAL_N, hipMemcpyHostToDevice));
+  bufs.restore_residents(kept);
   G = N;
 }
 

@@ -61,17 +61,17 @@ struct Minimiser {
   double gnatoms = 0.0;
   long long evals = 0;
   explicit Minimiser(Engine &en) : e(en) {
-    auto al = [&](Vec3 &v) { for (int a = 0; a < 3; ++a) { RX_HIP(hipMalloc(reinterpret_cast<void **>(&v.c[a]), sizeof(double) * e.NB)); RX_HIP(hipMemset(v.c[a], 0, sizeof(double) * e.NB)); } };
+    const size_t nb = static_cast<size_t>(e.NB);
+    auto al = [&](Vec3 &v) { for (int a = 0; a < 3; ++a) dev_alloc(v.c[a], nb, Fill::Zero); };
     al(P); al(G); al(Gold); al(snap.pos); al(snap.vel);
     if (e.ff.pqeq) al(snap.shl);          // PQEq: the shell displacements migrate with their atoms (comm.F90:153,165-167) and are relaxed by every trial solve
-    RX_HIP(hipMalloc(reinterpret_cast<void **>(&snap.q), sizeof(double) * e.NB)); RX_HIP(hipMalloc(reinterpret_cast<void **>(&snap.qsfp), sizeof(double) * e.NB));
-    RX_HIP(hipMalloc(reinterpret_cast<void **>(&snap.qsfv), sizeof(double) * e.NB)); RX_HIP(hipMalloc(reinterpret_cast<void **>(&snap.type), sizeof(int) * e.NB));
-    RX_HIP(hipMalloc(reinterpret_cast<void **>(&snap.gid), sizeof(long long) * e.NB));
+    dev_alloc(snap.q, nb, Fill::None); dev_alloc(snap.qsfp, nb, Fill::None); dev_alloc(snap.qsfv, nb, Fill::None);      // (save() writes what restore() reads)
+    dev_alloc(snap.type, nb, Fill::None); dev_alloc(snap.gid, nb, Fill::None);
   }
   ~Minimiser() {
-    auto fr = [](Vec3 &v) { for (int a = 0; a < 3; ++a) if (v.c[a]) (void)hipFree(v.c[a]); };
+    auto fr = [](Vec3 &v) { for (int a = 0; a < 3; ++a) dev_free(v.c[a]); };
     fr(P); fr(G); fr(Gold); fr(snap.pos); fr(snap.vel); fr(snap.shl);
-    (void)hipFree(snap.q); (void)hipFree(snap.qsfp); (void)hipFree(snap.qsfv); (void)hipFree(snap.type); (void)hipFree(snap.gid);
+    dev_free(snap.q); dev_free(snap.qsfp); dev_free(snap.qsfv); dev_free(snap.type); dev_free(snap.gid);
   }
   void copy3(Vec3 &dst, double *const src[3], int n) { for (int a = 0; a < 3; ++a) RX_HIP(hipMemcpyAsync(dst.c[a], src[a], sizeof(double) * n, hipMemcpyDeviceToDevice, e.stream)); }
   void copy3(double *const dst[3], const Vec3 &src, int n) { for (int a = 0; a < 3; ++a) RX_HIP(hipMemcpyAsync(dst[a], src.c[a], sizeof(double) * n, hipMemcpyDeviceToDevice, e.stream)); }

@@ -37,7 +37,7 @@ void Engine::rccl_init(const unsigned char id128[128], int rank, int world) {
   int nr = 0;
   RX_NCCL(ncclCommCount(c, &nr));
   if (nr != world) throw EngineError(RXMD_E_COMM, "RCCL communicator has " + std::to_string(nr) + " ranks, expected " + std::to_string(world));
-  if (!cnt_dev) { RX_HIP(hipMalloc(reinterpret_cast<void **>(&cnt_dev), 4 * sizeof(double))); RX_HIP(hipHostMalloc(reinterpret_cast<void **>(&cnt_host), 4 * sizeof(double))); }
+  if (!cnt_dev) { dev_alloc(cnt_dev, 4, Fill::None); cnt_host = static_cast<double *>(pinned_alloc(4 * sizeof(double), false)); }
 }
 
 // bounded wait (see engine.h): `query` polls the stream or the event
@@ -128,8 +128,8 @@ void Engine::pinned_wait(int nwords, unsigned seq, const char *what) {
 
 void Engine::rccl_destroy() {
   if (nccl) { (void)ncclCommDestroy(C(nccl)); nccl = nullptr; }
-  if (cnt_dev) { (void)hipFree(cnt_dev); cnt_dev = nullptr; }
-  if (cnt_host) { (void)hipHostFree(cnt_host); cnt_host = nullptr; }
+  dev_free(cnt_dev);
+  pinned_free(cnt_host); cnt_host = nullptr;
 }
 
 // one send_recv: nsend doubles of xbuf_send to `to`, the message of `from` into xbuf_recv; returns the doubles received

@@ -1101,7 +1101,7 @@ def test_random_velocities_mdmode_0_and_6():
 
 
 def test_poisoned_allocations():
-    """RXMD_POISON_ALLOC=1 (engine.hip): all engine memory starts as 0xFF bytes and the per-step scratch is re-filled with the pattern before every
+    """RXMD_POISON_ALLOC=1 (buffers.hip): all engine memory starts as 0xFF bytes and the per-step scratch is re-filled with the pattern before every
     rebuild.  RDX 2 x 2 x 2 and the SiC nanoparticle with PQEq, both QEq algebras, QEq + FORCE + MD steps against the oracle: nothing may read what
     nobody wrote (the reference's allocator does not clear either, module.F90:732-744; what it clears -- pot.F90:20-26, init.F90:117-131 -- the
     kernels clear).  The whole GPU suite was run once under the switch in round 4 (120 passed)."""
