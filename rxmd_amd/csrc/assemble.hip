@@ -167,7 +167,7 @@ void Engine::bonded_chain_begin() {
   RX_HIP(hipEventRecord(ev_bond, bond_stream));
 }
 
-void Engine::force(bool defer_host_read) {
+void Engine::force(bool defer_host_read, bool observe_energy) {
   if (!atoms_set) throw EngineError(RXMD_E_STATE, "atoms were never set");
   const KtPair t_force = outer_begin(&st.ms_force);
   if (!lists_valid) build_ghosts_and_lists();
@@ -177,7 +177,7 @@ void Engine::force(bool defer_host_read) {
     //  slow down by exactly what the chain saves -- 48.2-48.5 against 48.0-48.7 ms per step, the pass 1.02 against 0.82 ms -- so it starts here.)
     bonded_chain_begin();
     if (multi()) { on_comm_stream([&] { charge_halo(); }); join_comm_stream(); } else charge_halo();
-    { const bool kt = kt_begin(&st.ms_k_nonbond, &st.ms_nonbond); nonbonded(true); kt_end(kt); }        // pot.F90:48-52
+    { const bool kt = kt_begin(&st.ms_k_nonbond, &st.ms_nonbond); nonbonded(true, observe_energy); kt_end(kt); }        // pot.F90:48-52
     { const bool kt = kt_begin(&st.ms_bond_exposed); RX_HIP(hipStreamWaitEvent(stream, ev_bond, 0)); kt_end(kt); }   // what of the bonded chain ENbond did not hide
     st.bond_overlap = 1;
     k_add_force3<<<nblk(N, 256), 256, 0, stream>>>(N, fnb[0], fnb[1], fnb[2], frc[0], frc[1], frc[2]);
@@ -195,7 +195,7 @@ void Engine::force(bool defer_host_read) {
   if (multi()) on_comm_stream([&] { charge_halo(); }); else charge_halo();
   { const bool kt = kt_begin(&st.ms_k_bondorder, &st.ms_bo); bond_orders(); kt_end(kt); }
   if (multi()) join_comm_stream();
-  { const bool kt = kt_begin(&st.ms_k_nonbond, &st.ms_nonbond); if (ff.pqeq) nonbonded_pqeq(); else nonbonded(); kt_end(kt); }     // pot.F90:48-52
+  { const bool kt = kt_begin(&st.ms_k_nonbond, &st.ms_nonbond); if (ff.pqeq) nonbonded_pqeq(); else nonbonded(false, observe_energy); kt_end(kt); }     // pot.F90:48-52
   const KtPair t_bonded = outer_begin(&st.ms_bonded);
   bonded_energies();
   if (ff.pqeq) efield_force();                         // pot.F90:61, before ForceBondedTerms
@@ -532,7 +532,7 @@ void Engine::step(int nsteps) {
     { const bool kt = kt_begin(&st.ms_migrate); migrate(); kt_end(kt); }                                 // main.F90:75
     const int qs = cfg.qstep > 0 ? cfg.qstep : 1;
     if (step_count % qs == 0) qeq();                                     // main.F90:77-83
-    force(true);                                                         // main.F90:84 (energies read once, behind the last step)
+    force(true, s == nsteps - 1);                                        // main.F90:84 (energies read once, behind the last step: only that step forms ENbond's)
     accumulate_stress(true);                                             // main.F90:86-94
     k_kick<<<nblk(N, 256), 256, 0, stream>>>(N, dff, dt, Lex_w2, type, vel[0], vel[1], vel[2], frc[0], frc[1], frc[2], q, qsfp, qsfv);
     ++step_count;

@@ -1153,12 +1153,17 @@ __global__ void __launch_bounds__(256) k_ehb_donors(int N, unsigned donor_types,
   if (hm != 0u) don[static_cast<size_t>(reg) * region_cap + base + __popcll(m & ((1ULL << lane) - 1ULL))] = make_int2(i, static_cast<int>(hm));
 }
 
+// SLOTS: the build left the 4-byte entries out (lists.hip: needs_nb10).  A donor row's partners then come from its 2-byte window slots, as in
+// k_nonbond_win: position = first position of the slot's unit in the window of the row's group + offset in the unit, type from the cell-sorted type
+// bytes.  Both streams hold a row's entries at the same indices, so the candidates -- and the acceptor atomics -- come in the same order.
+template <bool SLOTS>
 __global__ void __launch_bounds__(256) k_ehb_sweep(int S10, DevFF ff, const int2 *__restrict__ don, const int *__restrict__ ndon, int region_cap, const int *__restrict__ boff, const int *__restrict__ nbr,
                                                     const int *__restrict__ type, const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
                                                     const double *__restrict__ bo0, const int *__restrict__ nb10, const int *__restrict__ n10, const double4 *__restrict__ pk, const int *__restrict__ perm,
                                                     double *__restrict__ cf1, double *__restrict__ fnx, double *__restrict__ fny, double *__restrict__ fnz,
                                                     double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ fz, double *__restrict__ pe,
-                                                    double *__restrict__ fsx, double *__restrict__ fsy, double *__restrict__ fsz
+                                                    double *__restrict__ fsx, double *__restrict__ fsy, double *__restrict__ fsz,
+                                                    const unsigned short *__restrict__ sl10, const int *__restrict__ rpos, const int *__restrict__ win_k, const unsigned char *__restrict__ stype, int G
 #ifdef RXMD_EHB_DEBUG
                                                     , int *dbg, int lim_n, int lim_b, int lim_nb
 #endif
@@ -1193,6 +1198,7 @@ __global__ void __launch_bounds__(256) k_ehb_sweep(int S10, DevFF ff, const int2
     EHB_CHECK(3, n, S10 + 1, i)
     const double xi = x[i], yi = y[i], zi = z[i];
     const size_t row = static_cast<size_t>(i) * S10;
+    const int *wk = SLOTS ? win_k + static_cast<size_t>(rpos[i] / WIN_ROWS) * WIN_MAXUNITS : nullptr;   // the window of the donor's group
     const int inx_l = (lane >= 1 && lane <= ff.nso && lane < 16) ? ff.inxn3hb[(ti * ff.n1 + 2) * ff.n1 + lane] : 0;
     if (lane < 16) { const DevHbP hp = ff.hb[inx_l]; s_hp[w][lane][0] = hp.r0hb; s_hp[w][lane][1] = hp.phb1; s_hp[w][lane][2] = hp.phb2; s_hp[w][lane][3] = hp.phb3; }   // (row 0 is never used: the compaction drops its candidates)
     int jl = 0; double bl = 0.0, xjl = 0.0, yjl = 0.0, zjl = 0.0;        // lane s holds atom, bond order and position of hydrogen slot s
@@ -1286,7 +1292,17 @@ __global__ void __launch_bounds__(256) k_ehb_sweep(int S10, DevFF ff, const int2
     for (int c0 = 0; c0 < n; c0 += 256) {                   // four batches of entry words requested together
       unsigned ent[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) { const int kk = c0 + 64 * u + lane; ent[u] = kk < n ? static_cast<unsigned>(nb10[row + kk]) : 0xffffffffu; }
+      for (int u = 0; u < 4; ++u) {
+        const int kk = c0 + 64 * u + lane;
+        if (SLOTS) {
+          ent[u] = 0xffffffffu;
+          if (kk < n) {
+            const int sl = sl10[row + kk] & 0x7fff;
+            const int pos = min(wk[sl / WIN_UNIT] + (sl & (WIN_UNIT - 1)), G - 1);
+            ent[u] = static_cast<unsigned>(pos) | (static_cast<unsigned>(stype[pos]) << NB10_IDX_BITS);
+          }
+        } else ent[u] = kk < n ? static_cast<unsigned>(nb10[row + kk]) : 0xffffffffu;
+      }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         if (c0 + 64 * u >= n) break;                                        // wave-uniform
@@ -1408,18 +1424,26 @@ void Engine::bonded_energies() {
     k_zero3<<<nblk(G, 256), 256, 0, stream>>>(G, fsort[0], fsort[1], fsort[2]);
     if (ehb_blocks_per_cu == 0) {                 // the persistent grid fills the device exactly: workgroups per CU from the kernel's own register / LDS footprint
       int nbk = 0;
-      RX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk, k_ehb_sweep, 256, 0));
+      RX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk, k_ehb_sweep<false>, 256, 0));
       ehb_blocks_per_cu = std::max(nbk, 1);
+      RX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk, k_ehb_sweep<true>, 256, 0));
+      ehb_blocks_per_cu_sl = std::max(nbk, 1);
     }
+    const bool slots = !nb10_valid;               // (then this build has its windows: build_ghosts_and_lists sweeps a build without either again)
+    const int ehb_grid = num_cu * (slots ? ehb_blocks_per_cu_sl : ehb_blocks_per_cu);
 #ifdef RXMD_EHB_DEBUG
     RX_HIP(hipMemsetAsync(ehb_cnt + EHB_REGIONS, 0, 4 * sizeof(int), stream));
-    k_ehb_sweep<<<num_cu * ehb_blocks_per_cu, 256, 0, stream>>>(S10, dff, ehb_don, ehb_cnt, region_cap, boff, nbr, type, pos[0], pos[1], pos[2], bo0, nb10, n10, sorted_xyzi, perm, cf1, fnx, fny, fnz, frc[0], frc[1], frc[2], pe_d, fsort[0], fsort[1], fsort[2], ehb_cnt + EHB_REGIONS, N, static_cast<int>(bcap), NB);
+#define RX_EHB(SL) k_ehb_sweep<SL><<<ehb_grid, 256, 0, stream>>>(S10, dff, ehb_don, ehb_cnt, region_cap, boff, nbr, type, pos[0], pos[1], pos[2], bo0, nb10, n10, sorted_xyzi, perm, cf1, fnx, fny, fnz, frc[0], frc[1], frc[2], pe_d, fsort[0], fsort[1], fsort[2], sl10, rpos, win_k, sorted_type, G, ehb_cnt + EHB_REGIONS, N, static_cast<int>(bcap), NB)
+    if (slots) RX_EHB(true); else RX_EHB(false);
+#undef RX_EHB
     { int hd[EHB_REGIONS + 4]; RX_HIP(hipMemcpyAsync(hd, ehb_cnt, sizeof(hd), hipMemcpyDeviceToHost, stream)); RX_HIP(hipStreamSynchronize(stream));
       for (int r = 1; r < EHB_REGIONS; ++r) hd[0] += hd[r];
       hd[4] = hd[EHB_REGIONS]; hd[5] = hd[EHB_REGIONS + 1]; hd[6] = hd[EHB_REGIONS + 2]; hd[7] = hd[EHB_REGIONS + 3];
       std::fprintf(stderr, "[ehb debug] donors %d  blocks/CU %d  first violation: code %d value %d aux %d lim %d   (N %d bcap %zu NB %d S10 %d rows10 %d)\n", hd[0], ehb_blocks_per_cu, hd[4], hd[5], hd[6], hd[7], N, bcap, NB, S10, rows10); }
 #else
-    k_ehb_sweep<<<num_cu * ehb_blocks_per_cu, 256, 0, stream>>>(S10, dff, ehb_don, ehb_cnt, region_cap, boff, nbr, type, pos[0], pos[1], pos[2], bo0, nb10, n10, sorted_xyzi, perm, cf1, fnx, fny, fnz, frc[0], frc[1], frc[2], pe_d, fsort[0], fsort[1], fsort[2]);
+#define RX_EHB(SL) k_ehb_sweep<SL><<<ehb_grid, 256, 0, stream>>>(S10, dff, ehb_don, ehb_cnt, region_cap, boff, nbr, type, pos[0], pos[1], pos[2], bo0, nb10, n10, sorted_xyzi, perm, cf1, fnx, fny, fnz, frc[0], frc[1], frc[2], pe_d, fsort[0], fsort[1], fsort[2], sl10, rpos, win_k, sorted_type, G)
+    if (slots) RX_EHB(true); else RX_EHB(false);
+#undef RX_EHB
 #endif
     k_add_sorted3<<<nblk(G, 256), 256, 0, stream>>>(G, perm, fsort[0], fsort[1], fsort[2], frc[0], frc[1], frc[2]);
   }

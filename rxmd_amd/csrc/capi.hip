@@ -502,6 +502,7 @@ int rxmd_hip_debug_get(rxmd_handle h, int what, double *out, int capacity) {
         RX_HIP(hipMemcpy(out + 1, e.hess + (e.S10 - 1), sizeof(double), hipMemcpyDeviceToHost));
         break;
       }
+      case 15: n = 2; if (capacity < 2) throw EngineError(RXMD_E_ARG, "capacity"); out[0] = e.nb10_valid ? 1.0 : 0.0; out[1] = e.nb10_sticky ? 1.0 : 0.0; break;   // the last list build wrote the 4-byte entries / a reader found them missing once (lists.hip: needs_nb10)
       case 13: {   // Est of the start vector and after every CG iteration of the last QEq call (what the reference prints with -DQEQDUMP, qeq.F90:117)
         n = static_cast<int>(e.est_trace.size()); if (capacity < n) throw EngineError(RXMD_E_ARG, "capacity");
         for (int k = 0; k < n; ++k) out[k] = e.est_trace[k];
@@ -511,6 +512,7 @@ int rxmd_hip_debug_get(rxmd_handle h, int what, double *out, int capacity) {
                    // back to the entry's own cell-sorted position and ghost flag through the group's window (== n10 when the window is right; -1: no windows)
         n = N; if (capacity < n) throw EngineError(RXMD_E_ARG, "capacity");
         if (!e.win_valid) { for (int i = 0; i < N; ++i) out[i] = -1.0; break; }
+        e.require_nb10();                                            // (a build that left the entries out is swept again; the engine keeps them from now on)
         RX_HIP(hipStreamSynchronize(e.stream));
         const size_t nrs = static_cast<size_t>(e.win_groups) * rxmd::WIN_ROWS;
         std::vector<int> c(N), rs(nrs), wc(e.win_groups), wk(static_cast<size_t>(e.win_groups) * rxmd::WIN_MAXUNITS);

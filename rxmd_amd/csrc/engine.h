@@ -242,6 +242,12 @@ struct Engine {
   int *cellid = nullptr, *cellid_sorted = nullptr, *perm = nullptr, *perm_in = nullptr, *cellstart = nullptr;
   double4 *sorted_xyzi = nullptr;   // cell-sorted (x,y,z,index-as-bits) copy of real positions
   unsigned char *sorted_type = nullptr;   // cell-sorted atom types (the window form of ENbond stages them next to the positions)
+  bool nb10_valid = false, nb10_sticky = false;   // this list build wrote the 4-byte entry stream / a reader once found it missing: every build writes it (lists.hip: needs_nb10)
+  bool needs_nb10(bool selfcheck) const;
+  bool sorted_w_charge = false;     // the w of the packed cell-sorted copy holds the charge (charge_halo) and no longer atom index | type (bin_cells), which the list sweeps read
+  void sorted_positions();          // the packed cell-sorted copy of the positions, w = atom index | type
+  void sorted_charge_only();
+  void require_nb10();              // called in front of every reader of nb10 but the hydrogen-bond sweep: sweeps the lists again with the stream on when this build left it out
   bool list_selfcheck = false;      // this list build: some box edge is shorter than two cut-offs, an atom can meet its own image
   void *cubtmp = nullptr; size_t cubtmp_bytes = 0;
   int *flags = nullptr, *scanout = nullptr;
@@ -263,7 +269,7 @@ struct Engine {
   double4 *e4b_t = nullptr; unsigned char *e4b_flag = nullptr; size_t e4b_cap = 0; bool e4b_dirty = false;
   void alloc_e4b_delivery(size_t entries);
   int nbonds_res = 0;                                                           // bonds of the residents = boff[N]: the first nbonds_res entries of the tables
-  int2 *ehb_don = nullptr; size_t ehb_don_cap = 0; int *ehb_cnt = nullptr; unsigned ehb_donor_types = 0u; int ehb_blocks_per_cu = 0; // hydrogen bonds (bonded.hip): donor list (atom, mask of its hydrogen slots), its length, types X with a row (X, H = 2, any)
+  int2 *ehb_don = nullptr; size_t ehb_don_cap = 0; int *ehb_cnt = nullptr; unsigned ehb_donor_types = 0u; int ehb_blocks_per_cu = 0, ehb_blocks_per_cu_sl = 0; // (_sl: of the sweep over the window slots) hydrogen bonds (bonded.hip): donor list (atom, mask of its hydrogen slots), its length, types X with a row (X, H = 2, any)
   double *deltap = nullptr, *delta = nullptr, *nlp = nullptr, *dDlp = nullptr, *deltalp = nullptr;
   double *cds = nullptr, *cd = nullptr, *cc_ = nullptr;
   // 10 A list
@@ -326,7 +332,9 @@ struct Engine {
   bool rows_split_pending_invalid() const { return n_bnd < 0 || n_bnd > N; }
   bool sums_from_list = false;     // the list sweep left H.(qs,qt) of the CG start vector in sall / sgh
   void qeq();
-  void force(bool defer_host_read = false);   // defer: the energies stay in the pinned buffer until finish_force() (step(): no host wait between FORCE and the next step)
+  // observe_energy = false (Engine::step, every step but the last of a call): nothing reads this FORCE's energies -- ENbond skips its pair and self
+  // energies, PE(11:13) stay 0 in the block that the next observed FORCE overwrites.  Forces and the virial (astr accumulates over steps) are untouched.
+  void force(bool defer_host_read = false, bool observe_energy = true);   // defer: the energies stay in the pinned buffer until finish_force() (step(): no host wait between FORCE and the next step)
   void finish_force();
   bool force_pending = false;
   // run-ahead CG loop (qeq.hip): the scalars of an iteration reach the host as a snapshot the update kernel's tail writes straight into pinned host memory
@@ -449,7 +457,7 @@ struct Engine {
   void bond_orders();
   void bonded_energies();
   void charge_halo();
-  void nonbonded(bool to_fnb = false);
+  void nonbonded(bool to_fnb = false, bool energy = true);
   void pqeq_sorted_shells();      // ghost shells <- owners, cell-sorted copy (MODE_COPY payload of spos, comm.F90:129-131)
   void pqeq_update_shells();      // update_shell_positions, pqeq.F90:184-259
   bool pq_matrix_stale = false;   // PQEq: the shells have moved (end of a PQEq call) since the 10 A list formed its shell-core values and field term from them

@@ -1480,8 +1480,12 @@ void Engine::bin_cells() {
   while ((1LL << bits) < grid.nfine + 1 && bits < 31) ++bits;
   RX_HIP(hipcub::DeviceRadixSort::SortPairs(cubtmp, tb, cellid, cellid_sorted, perm_in, perm, G, 0, bits, stream));
   k_cell_starts<<<nblk(grid.nfine + 1, 256), 256, 0, stream>>>(G, grid.nfine, cellid_sorted, cellstart);
-  k_sorted_pos<<<nblk(G, 256), 256, 0, stream>>>(G, N, perm, groot, pos[0], pos[1], pos[2], type, sorted_xyzi, sorted_type, rootperm, invpos);
+  sorted_positions();
   if (ff.pqeq) pqeq_sorted_shells();
+}
+void Engine::sorted_positions() {
+  k_sorted_pos<<<nblk(G, 256), 256, 0, stream>>>(G, N, perm, groot, pos[0], pos[1], pos[2], type, sorted_xyzi, sorted_type, rootperm, invpos);
+  sorted_w_charge = false;
 }
 
 void Engine::sorted_copy(const double2 *v) {
@@ -1540,9 +1544,10 @@ void Engine::build_ghosts_and_lists(bool qeq_prepass) {
   win_groups = h_err[8];                               // groups of this build (build_windows; the sweep ran over the host-side bound)
   max_row10 = h_err[3]; min_row10 = std::min(h_err[4], h_err[3]);   // longest / shortest 10 A row of this build (k_list10)
   win_maxunits = h_err[5]; win_valid = win_groups > 0 && h_err[6] == 0 && win_maxunits > 0 && (!multi() || (win_nbnd >= 0 && win_nbnd <= win_groups)) && !opt.spmv_no_win;   // window form of the matrix (build_windows)
+  lists_valid = true;
+  if (!nb10_valid && !win_valid) require_nb10();       // the windows were lost in a build that counted on them: the row forms need the 4-byte entries (lists.hip: needs_nb10)
   collect_timers();
   outer_end(t_lists);
-  lists_valid = true;
   pq_matrix_stale = false;
 }
 

@@ -377,8 +377,6 @@ __global__ void __launch_bounds__(64 * L10_ROWS) k_list10(int N, int S10, Grid g
 #endif
           __builtin_nontemporal_store(static_cast<unsigned short>((k - cE[t_]) | (j >= N ? 0x8000 : 0)), sl10 + row + slot);     // cE: first position of the column's interval - 8 x its first unit
         }
-        unsigned ent = static_cast<unsigned>(k) | (static_cast<unsigned>(tj) << NB10_IDX_BITS) | (j >= N ? NB10_GHOST : 0u);
-        if (SELFCHECK && gid[j] == gid[i]) ent |= NB10_SELF;           // an atom and its own periodic image (small boxes only)
         if (xs0) {
           const double qsj = xs0[k].x;
           ra += h * qsj;
@@ -388,7 +386,11 @@ __global__ void __launch_bounds__(64 * L10_ROWS) k_list10(int N, int S10, Grid g
 #ifdef RXMD_EXPERIMENTS
         if (!(g.probe & 8))
 #endif
-        __builtin_nontemporal_store(static_cast<int>(ent), nb10 + row + slot);      // the three streams are written once and read by other kernels: past the L2, which holds the table nodes
+        if (nb10) {                                                     // (wave-uniform; nullptr: no kernel of this build reads the 4-byte entries, Engine::needs_nb10)
+          unsigned ent = static_cast<unsigned>(k) | (static_cast<unsigned>(tj) << NB10_IDX_BITS) | (j >= N ? NB10_GHOST : 0u);
+          if (SELFCHECK && gid[j] == gid[i]) ent |= NB10_SELF;         // an atom and its own periodic image (small boxes only)
+          __builtin_nontemporal_store(static_cast<int>(ent), nb10 + row + slot);    // the three streams are written once and read by other kernels: past the L2, which holds the table nodes
+        }
 #ifdef RXMD_EXPERIMENTS
         if (!(g.probe & 16))
 #endif
@@ -503,7 +505,7 @@ __global__ void __launch_bounds__(64 * L10_ROWS) k_list10(int N, int S10, Grid g
   if (qn > 0) emit(qn);
   if (live) {
   if (cnt > S10) { if (lane == 0) { atomicMax(&err[1], cnt); atomicCAS(&err[0], DERR_NONE, DERR_MAXN10); } cnt = S10; }  // qeq.F90:248-252
-  if (lane < 4 && cnt + lane < ((cnt + 3) & ~3)) { nb10[row + cnt + lane] = 0; hess[row + cnt + lane] = 0.0; sl10[row + cnt + lane] = 0; }   // zero-pad the row to a multiple of 4 (value 0, slot 0)
+  if (lane < 4 && cnt + lane < ((cnt + 3) & ~3)) { if (nb10) nb10[row + cnt + lane] = 0; hess[row + cnt + lane] = 0.0; sl10[row + cnt + lane] = 0; }   // zero-pad the row to a multiple of 4 (value 0, slot 0)
   if (xs0) {
     ra = wave_sum_l(ra); rg = wave_sum_l(rg);
     if (lane == 0) { s_all[i] = make_double2(ra, 0.0); s_gh[i] = make_double2(rg, 0.0); }
@@ -553,13 +555,15 @@ __global__ void k_col_groups(int ncol, int nzf, const int *__restrict__ cellstar
   colg[c] = c < ncol ? (rank[cellstart[(c + 1) * nzf]] - rank[cellstart[c * nzf]] + WIN_ROWS - 1) / WIN_ROWS : 0;
 }
 __global__ void k_rows_sorted(int G, int N, int nzf, const int *__restrict__ perm, const int *__restrict__ rank, const int *__restrict__ cid_sorted, const int *__restrict__ cellstart,
-                              const int *__restrict__ colgo, int *__restrict__ rows_sorted, int ncol, int *__restrict__ err) {
+                              const int *__restrict__ colgo, int *__restrict__ rows_sorted, int *__restrict__ rpos, int ncol, int *__restrict__ err) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k == 0) err[8] = colgo[ncol];                              // groups of this build: the sweep's workgroups beyond it leave at once; the host reads it with the error word
   if (k >= G || perm[k] >= N) return;
   const int c = cid_sorted[k] / nzf;
   const int r = rank[k] - rank[cellstart[c * nzf]];              // this resident's place among the residents of its column
-  rows_sorted[(colgo[c] + r / WIN_ROWS) * WIN_ROWS + (r % WIN_ROWS)] = perm[k];
+  const int place = (colgo[c] + r / WIN_ROWS) * WIN_ROWS + (r % WIN_ROWS);
+  rows_sorted[place] = perm[k];
+  rpos[perm[k]] = place;                                         // the inverse: a resident's window group is rpos / WIN_ROWS (hydrogen-bond sweep over the slots; the row order of the CG loop)
 }
 __global__ void k_split_groups(int ng, const int *__restrict__ flag, const int *__restrict__ scan, int *__restrict__ g_int, int *__restrict__ g_bnd) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -577,7 +581,7 @@ void Engine::build_windows() {
   k_col_groups<<<nblk(ncol + 1, 256), 256, 0, stream>>>(ncol, grid.nzf, cellstart, scanout2, flags);     // (flags / scanout: free until the sweep writes its row flags)
   tb = cubtmp_bytes;
   RX_HIP(hipcub::DeviceScan::ExclusiveSum(cubtmp, tb, flags, scanout, ncol + 1, stream));
-  k_rows_sorted<<<nblk(G, 256), 256, 0, stream>>>(G, N, grid.nzf, perm, scanout2, cellid_sorted, cellstart, scanout, rows_sorted, ncol, d_err);
+  k_rows_sorted<<<nblk(G, 256), 256, 0, stream>>>(G, N, grid.nzf, perm, scanout2, cellid_sorted, cellstart, scanout, rows_sorted, rpos, ncol, d_err);
 }
 
 // The words a list build starts from, in ONE launch (until round 6: nine 4-byte memsets of ~5 us each, spread over the build): the error word's
@@ -602,6 +606,35 @@ void Engine::build_bonded_list(bool pack_only) {
   k_bond_csr<<<dim3(nblk(G, 32), (MAXNB + 7) / 8), 256, 0, stream>>>(G, N, NB, static_cast<long long>(bcap), nbr_sm, nbrcnt, boff, nbr, brev, bown, type, btype, d_err);
 }
 
+// The 4-byte entry stream nb10 (cell-sorted position | type | flags per entry: 1.7 GB per build at 980 k atoms) is written only for a build whose
+// kernels read it.  The window forms of the matrix pass and of ENbond read the 2-byte slots, and the hydrogen-bond sweep finds a donor row's partners
+// through the slots and the group's window (bonded.hip); the readers of the entries are the row forms (k_spmv, k_nonbond), the PQEq kernels, the
+// self-image flag of small boxes and debug tap 11.  Decided on the host BEFORE the sweep, so from the previous build's windows: a build that loses
+// its windows after one that had them is swept again with the stream on (build_ghosts_and_lists), and require_nb10() does the same for a reader
+// that finds the stream missing -- from then on the engine always writes it.
+bool Engine::needs_nb10(bool selfcheck) const {
+#ifdef RXMD_EXPERIMENTS
+  return true;                                     // (the probes of experiments.hip read the entries)
+#endif
+  return nb10_sticky || opt.nb10_always || ff.pqeq || selfcheck || opt.spmv_win == 0 || opt.nonbond_win == 0 || opt.spmv_no_win || !win_valid;
+}
+void Engine::require_nb10() {
+  if (nb10_valid) return;
+  nb10_sticky = true;
+  if (!lists_valid) return;                        // (the next build writes it)
+  // the sweep again, in stream order behind whatever reads the lists now: the same rows, values, slots and windows, plus the entries.  The words the
+  // host took from the first sweep stay (h_err: the same numbers); the row sums of the CG start vector are not formed again (xs may have moved on)
+  // The sweep takes atom index and type of a candidate from the w of the packed cell-sorted copy, where FORCE has put the charges since: the copy is
+  // formed again first (the positions have not moved: the lists are valid) and gets its charges back behind the sweep.
+  const bool wv = win_valid, sfl = sums_from_list, retry = list10_retry, wq = sorted_w_charge;
+  const int wg = win_groups;
+  if (wq) sorted_positions();
+  sums_from_list = false; list10_retry = true;
+  try { build_list10(); } catch (...) { sums_from_list = sfl; list10_retry = retry; throw; }
+  sums_from_list = sfl; list10_retry = retry; win_valid = wv; win_groups = wg;
+  if (wq) sorted_charge_only();
+}
+
 constexpr int L10_ROWS_LAUNCH = L10_ROWS;
 void Engine::build_list10() {
   grid.probe = static_cast<int>(opt.list_probe);    // (experiments build only: 0 otherwise)
@@ -609,10 +642,12 @@ void Engine::build_list10() {
   // an atom can meet its own image within rctap only if some box edge is shorter than 2*rctap
   const bool selfcheck = (grid.wid[0] < 2.0 * ff.rctap + 1.0) || (grid.wid[1] < 2.0 * ff.rctap + 1.0) || (grid.wid[2] < 2.0 * ff.rctap + 1.0);
   list_selfcheck = selfcheck;
+  int *const nb10_w = needs_nb10(selfcheck) ? nb10 : nullptr;       // (win_valid: still the previous build's)
+  nb10_valid = nb10_w != nullptr;
 #define RX_LIST10(SC, PQF) do { if (grid.ortho) RX_LIST10_O(SC, PQF, true); else RX_LIST10_O(SC, PQF, false); } while (0)
 #define RX_LIST10_O(SC, PQF, OR)                                                                                                               \
   k_list10<SC, PQF, OR><<<std::max(win_groups, 1) * (WIN_ROWS / L10_ROWS_LAUNCH), 64 * L10_ROWS_LAUNCH, 0, stream>>>(N, S10, grid, rmesh, dff, cellid, cellstart, sorted_xyzi, pos[0], pos[1], pos[2], spos[0], spos[1], spos[2], type, gid, \
-                                                    nb10, hess, n10, d_err, sorted_shl, shl[0], shl[1], shl[2], hsc, pqrow, sums_from_list ? xs : nullptr, sall, sgh, multi() ? flags : nullptr, \
+                                                    nb10_w, hess, n10, d_err, sorted_shl, shl[0], shl[1], shl[2], hsc, pqrow, sums_from_list ? xs : nullptr, sall, sgh, multi() ? flags : nullptr, \
                                                     rows_sorted, sl10, rowcols, grp_base, gflag)
   win_valid = false;
   build_windows();

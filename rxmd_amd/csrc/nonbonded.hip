@@ -23,7 +23,11 @@ __global__ void k_sorted_charge(int G, const int *__restrict__ rootperm, const d
 __device__ inline double wave_sum_n(double v) { return wave_sum64(v); }   // DPP reduction, engine.h
 
 // one pair of a row: r^2, the table node of the type pair, energies (half of the pair from each side), force on the row's atom, pair virial
+// ENERGY = false (a step of Engine::step whose energies nobody reads, Engine::force): the pair energies drop out -- the energy half of the table
+// node is not loaded, e11 / e12 are neither accumulated nor summed over the wavefront, the self energy and the three energy atomics are skipped.
+// The force and the virial (astr accumulates over the steps) are the same instructions on the same operands: the same bits.
 struct NbAcc { double f0, f1, f2, v0, v1, v2, v3, v4, v5, e11, e12; };
+template <bool ENERGY>
 __device__ inline void nb_pair(const DevFF &ff, const int *__restrict__ ix2, double xi, double yi, double zi, double qi, const double4 &pj, int tj, NbAcc &a) {
   const double d0 = xi - pj.x, d1 = yi - pj.y, d2 = zi - pj.z;
   const double r2 = d0 * d0 + d1 * d1 + d2 * d2;
@@ -37,8 +41,10 @@ __device__ inline void nb_pair(const DevFF &ff, const int *__restrict__ ix2, dou
   const double CEvdw = nd.CEvdw + t * nd.dCEvdw_;
   const double CEclmb = (nd.CEclmb + t * nd.dCEclmb_) * qij;
   // every pair sits in two rows (i's and its partner's): half of the pair energy from each side
-  a.e11 += 0.5 * (nd.Evdw + t * nd.dEvdw_);
-  a.e12 += 0.5 * (nd.Eclmb + t * nd.dEclmb_) * qij;
+  if (ENERGY) {
+    a.e11 += 0.5 * (nd.Evdw + t * nd.dEvdw_);
+    a.e12 += 0.5 * (nd.Eclmb + t * nd.dEclmb_) * qij;
+  }
   const double c = CEvdw + CEclmb;
   a.f0 -= c * d0; a.f1 -= c * d1; a.f2 -= c * d2;
   const double hc = -0.5 * c;
@@ -51,6 +57,7 @@ __device__ inline void nb_pair(const DevFF &ff, const int *__restrict__ ix2, dou
 #ifndef NB_WPB
 #define NB_WPB 8      // rows per workgroup (measured 4.08 / 3.73 / 4.35 ms at 4 / 8 / 16)
 #endif
+template <bool ENERGY>
 __global__ void __launch_bounds__(64 * NB_WPB) k_nonbond(int N, int S10, DevFF ff, const int *__restrict__ nb10, const int *__restrict__ n10,
                                                   const double4 *__restrict__ pk, const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
                                                   const double *__restrict__ q, const int *__restrict__ type,
@@ -76,7 +83,7 @@ __global__ void __launch_bounds__(64 * NB_WPB) k_nonbond(int N, int S10, DevFF f
       for (int u = 0; u < NB_UNR; ++u) {
         const unsigned e = ee[u];
         if (e & NB10_SELF) continue;                                    // padding, or the atom's own periodic image (pot.F90:715)
-        nb_pair(ff, ix2, xi, yi, zi, qi, pk[e & NB10_IDX_MASK], static_cast<int>((e >> NB10_IDX_BITS) & 15u), acc);
+        nb_pair<ENERGY>(ff, ix2, xi, yi, zi, qi, pk[e & NB10_IDX_MASK], static_cast<int>((e >> NB10_IDX_BITS) & 15u), acc);
       }
     }
     e11 = acc.e11; e12 = acc.e12;
@@ -89,15 +96,16 @@ __global__ void __launch_bounds__(64 * NB_WPB) k_nonbond(int N, int S10, DevFF f
     if (lane == 0) {
       if (assign) { fx[i] = f0; fy[i] = f1; fz[i] = f2; }                  // (the bonded chain owns the force array meanwhile: Engine::force adds these behind the join)
       else { fx[i] += f0; fy[i] += f1; fz[i] += f2; }
-      const DevAtomP ap = ff.atom[ti];
-      e13 = CEchrge * (ap.chi * qi + 0.5 * ap.eta * qi * qi);           // pot.F90:708
+      if (ENERGY) { const DevAtomP ap = ff.atom[ti]; e13 = CEchrge * (ap.chi * qi + 0.5 * ap.eta * qi * qi); }   // pot.F90:708
       sv[w][0] = v0 - xi * f0; sv[w][1] = v1 - yi * f1; sv[w][2] = v2 - zi * f2; sv[w][3] = v3 - yi * f2; sv[w][4] = v4 - zi * f0; sv[w][5] = v5 - xi * f1;
     }
   }
-  e11 = wave_sum_n(e11); e12 = wave_sum_n(e12); e13 = wave_sum_n(e13);
-  if (lane == 0) { sm[w][0] = e11; sm[w][1] = e12; sm[w][2] = e13; }
+  if (ENERGY) {
+    e11 = wave_sum_n(e11); e12 = wave_sum_n(e12); e13 = wave_sum_n(e13);
+    if (lane == 0) { sm[w][0] = e11; sm[w][1] = e12; sm[w][2] = e13; }
+  }
   __syncthreads();
-  if (threadIdx.x < 3) {
+  if (ENERGY && threadIdx.x < 3) {
     double s = 0.0;
     for (int k = 0; k < NB_WPB; ++k) s += sm[k][threadIdx.x];
     if (s != 0.0) atomicAdd(pe + 11 + threadIdx.x, s);
@@ -118,6 +126,7 @@ __global__ void __launch_bounds__(64 * NB_WPB) k_nonbond(int N, int S10, DevFF f
 // k_nonbond: forces and energies are bit for bit the same.  Not for boxes in which an atom meets its own image (the slot has no bit for that).
 // LDS holds the first `maxunits` units of a window (33 bytes per slot; 296 units = 78 KB: two workgroups per CU); the few groups with a larger
 // window (328 units is the largest of the RDX run, ~250 the mean) fetch the partners beyond it from the cell-sorted arrays as k_nonbond does.
+template <bool ENERGY>
 __global__ void __launch_bounds__(64 * WIN_ROWS, 8) k_nonbond_win(int N, int G, int S10, DevFF ff, const unsigned short *__restrict__ sl10, const int *__restrict__ n10,
                                                                 const int *__restrict__ rows_sorted, const int *__restrict__ win_k, const int *__restrict__ win_cnt, int maxunits,
                                                                 const double4 *__restrict__ pk, const unsigned char *__restrict__ stype,
@@ -157,8 +166,8 @@ __global__ void __launch_bounds__(64 * WIN_ROWS, 8) k_nonbond_win(int N, int G, 
       for (int u = 0; u < NB_UNR; ++u) {
         if (ee[u] == 0xffffu) continue;                                  // behind the row's end (no slot is that large)
         const int sl = static_cast<int>(ee[u] & 0x7fffu);
-        if (sl < capslots) nb_pair(ff, ix2, xi, yi, zi, qi, s_p[sl], static_cast<int>(s_t[sl]), acc);
-        else { const int pos = min(wk[sl / WIN_UNIT] + (sl & (WIN_UNIT - 1)), G - 1); nb_pair(ff, ix2, xi, yi, zi, qi, pk[pos], static_cast<int>(stype[pos]), acc); }
+        if (sl < capslots) nb_pair<ENERGY>(ff, ix2, xi, yi, zi, qi, s_p[sl], static_cast<int>(s_t[sl]), acc);
+        else { const int pos = min(wk[sl / WIN_UNIT] + (sl & (WIN_UNIT - 1)), G - 1); nb_pair<ENERGY>(ff, ix2, xi, yi, zi, qi, pk[pos], static_cast<int>(stype[pos]), acc); }
       }
     }
     e11 = acc.e11; e12 = acc.e12;
@@ -167,15 +176,16 @@ __global__ void __launch_bounds__(64 * WIN_ROWS, 8) k_nonbond_win(int N, int G, 
     if (lane == 0) {
       if (assign) { fx[i] = f0; fy[i] = f1; fz[i] = f2; }                  // (the bonded chain owns the force array meanwhile: Engine::force adds these behind the join)
       else { fx[i] += f0; fy[i] += f1; fz[i] += f2; }
-      const DevAtomP ap = ff.atom[ti];
-      e13 = CEchrge * (ap.chi * qi + 0.5 * ap.eta * qi * qi);           // pot.F90:708
+      if (ENERGY) { const DevAtomP ap = ff.atom[ti]; e13 = CEchrge * (ap.chi * qi + 0.5 * ap.eta * qi * qi); }   // pot.F90:708
       sv[w][0] = v0 - xi * f0; sv[w][1] = v1 - yi * f1; sv[w][2] = v2 - zi * f2; sv[w][3] = v3 - yi * f2; sv[w][4] = v4 - zi * f0; sv[w][5] = v5 - xi * f1;   // the stress note of k_nonbond
     }
   }
-  e11 = wave_sum_n(e11); e12 = wave_sum_n(e12); e13 = wave_sum_n(e13);
-  if (lane == 0) { sm[w][0] = e11; sm[w][1] = e12; sm[w][2] = e13; }
+  if (ENERGY) {
+    e11 = wave_sum_n(e11); e12 = wave_sum_n(e12); e13 = wave_sum_n(e13);
+    if (lane == 0) { sm[w][0] = e11; sm[w][1] = e12; sm[w][2] = e13; }
+  }
   __syncthreads();
-  if (threadIdx.x < 3) {
+  if (ENERGY && threadIdx.x < 3) {
     double s = 0.0;
     for (int k = 0; k < WIN_ROWS; ++k) s += sm[k][threadIdx.x];
     if (s != 0.0) atomicAdd(pe + 11 + threadIdx.x, s);
@@ -188,8 +198,11 @@ __global__ void __launch_bounds__(64 * WIN_ROWS, 8) k_nonbond_win(int N, int G, 
   }
 }
 
+// the w of the packed copy from the charges as they are, no exchange (require_nb10: the list sweep needs atom index and type there, the kernels of FORCE the charge)
+void Engine::sorted_charge_only() { k_sorted_charge<<<nblk(G, 256), 256, 0, stream>>>(G, multi() ? perm : rootperm, q, sorted_xyzi); sorted_w_charge = true; }
 // ghost charges (MODE_COPY payload, comm.F90:135) and their cell-sorted copy; multi-rank: through the staged exchange
 void Engine::charge_halo() {
+  sorted_w_charge = true;
   if (multi()) {
     halo_staged(q, 1);
     k_sorted_charge<<<nblk(G, 256), 256, 0, stream>>>(G, perm, q, sorted_xyzi);
@@ -197,7 +210,7 @@ void Engine::charge_halo() {
     k_sorted_charge<<<nblk(G, 256), 256, 0, stream>>>(G, rootperm, q, sorted_xyzi);
 }
 
-void Engine::nonbonded(bool to_fnb) {
+void Engine::nonbonded(bool to_fnb, bool energy) {
   double *f0 = to_fnb ? fnb[0] : frc[0], *f1 = to_fnb ? fnb[1] : frc[1], *f2 = to_fnb ? fnb[2] : frc[2];
   const int assign = to_fnb ? 1 : 0;
   // over the windows of the matrix pass when this list build has them and no atom can meet its own image (RXMD_NONBOND_WIN=0: the row form)
@@ -205,12 +218,16 @@ void Engine::nonbonded(bool to_fnb) {
   const int units = std::min(win_maxunits, 296);                         // 296 units x 8 slots x 33 bytes = 78 KB: two workgroups per CU
   const size_t lds = static_cast<size_t>(units) * WIN_UNIT * (sizeof(double4) + 1) + 16;
   if (win_valid && win_env && !list_selfcheck) {
-    k_nonbond_win<<<win_groups, 64 * WIN_ROWS, lds, stream>>>(N, G, S10, dff, sl10, n10, rows_sorted, win_k, win_cnt, units, sorted_xyzi, sorted_type, pos[0], pos[1], pos[2], q, type,
-                                                             f0, f1, f2, scal + 32, assign);
+#define RX_NB_WIN(EN) k_nonbond_win<EN><<<win_groups, 64 * WIN_ROWS, lds, stream>>>(N, G, S10, dff, sl10, n10, rows_sorted, win_k, win_cnt, units, sorted_xyzi, sorted_type, pos[0], pos[1], pos[2], q, type, \
+                                                                 f0, f1, f2, scal + 32, assign)
+    if (energy) RX_NB_WIN(true); else RX_NB_WIN(false);
+#undef RX_NB_WIN
     RX_HIP(hipGetLastError());
     return;
   }
-  k_nonbond<<<nblk(N, NB_WPB), 64 * NB_WPB, 0, stream>>>(N, S10, dff, nb10, n10, sorted_xyzi, pos[0], pos[1], pos[2], q, type, f0, f1, f2, scal + 32, assign);
+  require_nb10();                                  // the row form reads the 4-byte entries
+  if (energy) k_nonbond<true><<<nblk(N, NB_WPB), 64 * NB_WPB, 0, stream>>>(N, S10, dff, nb10, n10, sorted_xyzi, pos[0], pos[1], pos[2], q, type, f0, f1, f2, scal + 32, assign);
+  else k_nonbond<false><<<nblk(N, NB_WPB), 64 * NB_WPB, 0, stream>>>(N, S10, dff, nb10, n10, sorted_xyzi, pos[0], pos[1], pos[2], q, type, f0, f1, f2, scal + 32, assign);
 }
 
 }  // namespace rxmd

@@ -105,9 +105,11 @@ __global__ void k_sorted_charge_p(int G, const int *__restrict__ rootperm, const
 
 void Engine::pqeq_update_shells() {
   // partner charges: final q of this PQEq call, ghosts resolved (the reference's q(j) after the last QCOPY)
+  sorted_w_charge = true;
   if (multi()) { halo_staged(q, 1); k_sorted_charge_p<<<nblk(G, 256), 256, 0, stream>>>(G, perm, q, sorted_xyzi); }
   else k_sorted_charge_p<<<nblk(G, 256), 256, 0, stream>>>(G, rootperm, q, sorted_xyzi);
   // new shells into scratch (every row reads its partners' old shells), then copy back
+  require_nb10();
   k_shell_update<<<nblk(N, 4), 256, 0, stream>>>(N, S10, dff, nb10, n10, sorted_xyzi, sorted_shl, pos[0], pos[1], pos[2], type, shl[0], shl[1], shl[2], cds, cd, cc_,
                                                 cfg.efield_dir, cfg.efield_strength * 23.060538);
   double *tmp[3] = {cds, cd, cc_};
@@ -217,6 +219,7 @@ void Engine::efield_force() {
 }
 
 void Engine::nonbonded_pqeq() {
+  require_nb10();
   k_nonbond_pqeq<<<nblk(N, 4), 256, 0, stream>>>(N, S10, dff, nb10, n10, sorted_xyzi, sorted_shl, pos[0], pos[1], pos[2], q, type, shl[0], shl[1], shl[2],
                                                 frc[0], frc[1], frc[2], scal + 32);
 }

@@ -644,6 +644,7 @@ void Engine::qeq() {
     const int rbl = rowlist ? nblk(nrows, SPMV_WPB) : rb;
     if (rbl == 0) return 0;
     st.spmv_nstep = 0; st.spmv_var = 0;
+    require_nb10();                              // the row form reads the 4-byte entries
 #define RX_PASS3(M, S, P, PI) k_spmv<M, S, P, PI><<<rbl, 64 * SPMV_WPB, 0, stream>>>(N, S10, dff, nb10, hess, n10, xs, hst, gst, qst, q, type, scal, partials, ra, rg, hsc, pqrow, swz, rowlist, nrows, pbase, stopflag)
 #define RX_PASS(M, S)                                                                                                  \
   do {                                                                                                                 \
