@@ -206,6 +206,18 @@ module rxmd_hip_mod
        real(c_double), intent(out) :: p6_GPa(6), mu(3), volume
        integer(c_long_long), intent(out) :: couplings
      end function
+     ! mixed-precision charge solver: matrix_bits 64 (default) or 32 = the QEq matrix values rounded once to REAL(4) and streamed as
+     ! float by the window pass, all arithmetic in double (plain QEq only; takes effect at the next QEq call)
+     integer(c_int) function rxmd_hip_set_qeq_precision(h, matrix_bits) bind(c, name='rxmd_hip_set_qeq_precision')
+       import :: c_ptr, c_int
+       type(c_ptr), value :: h
+       integer(c_int), value :: matrix_bits
+     end function
+     integer(c_int) function rxmd_hip_get_qeq_precision(h, requested_bits, in_use_bits) bind(c, name='rxmd_hip_get_qeq_precision')
+       import :: c_ptr, c_int
+       type(c_ptr), value :: h
+       integer(c_int), intent(out) :: requested_bits, in_use_bits
+     end function
   end interface
 
 contains

@@ -149,6 +149,21 @@ int rxmd_hip_set_barostat(rxmd_handle h, int mode, int axes, const double p0_GPa
 /* last coupling: pressure tensor (xx,yy,zz,yz,zx,xy) [GPa], mu[3], volume [A^3] the pressure was computed at, number of couplings so far */
 int rxmd_hip_get_barostat(rxmd_handle h, double p6_GPa[6], double mu[3], double *volume, long long *couplings);
 
+/* ---- mixed-precision charge solver: the QEq matrix values streamed as REAL(4) --------------- */
+/* matrix_bits 64 (default): the path as it always was.  32: the list sweep rounds every value of the 10 A matrix ONCE to REAL(4) and the
+ * window pass of the CG streams the values as float (6 instead of 10 bytes per entry); every product, sum, vector and scalar stays
+ * double, and the row pass and the row sums of the CG start vector use the same rounded values, so every form of the pass applies one
+ * operator.  The solution is the fixed point of the rounded matrix: against the full-precision one charges differ by ~5e-7 and forces by
+ * ~8e-6 in the parity metric (max |dq| 2.3e-7 e, max |df| 1e-5 kcal/mol/A on RDX), energy terms by <= 2.5e-7 and the total PE by 4e-11
+ * relative (QEq is variational).  May be called at any time; takes effect at the next QEq call (the lists are invalidated and the 10 A
+ * streams allocated again).  The placement search of the window pass is off while 32 is requested (rxmd_stats.place_draws = 0).
+ * RXMD_E_ARG: any other value, or 32 on an engine created with pqeq_path (PQEq carries a second value stream: not supported).
+ * RXMD_QEQ_F32=1 in the environment: a plain-QEq engine starts with 32 requested (ignored for PQEq).
+ * get: *requested_bits = what was asked for; *in_use_bits = width of the value stream the last matrix pass read -- 32 only when the
+ * float instance of the window pass ran (the row pass, RXMD_SPMV_WIN=0 or a window that does not fit, reads the double stream: 64). */
+int rxmd_hip_set_qeq_precision(rxmd_handle h, int matrix_bits);
+int rxmd_hip_get_qeq_precision(rxmd_handle h, int *requested_bits, int *in_use_bits);
+
 /* ---- the same path behind the reference's own argument shapes ------------------------------- */
 /* Host arrays in the reference layout: atype(NBUFFER) packed type+gid*1e-13, pos/f(NBUFFER,3)
  * column-major REAL coordinates, residents 1..natoms.  These upload, run the device path and

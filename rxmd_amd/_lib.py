@@ -76,6 +76,8 @@ SYMBOLS = [
     ("rxmd_hip_get_lattice", C.c_int, [H, PD]),
     ("rxmd_hip_set_barostat", C.c_int, [H, C.c_int, C.c_int, PD, C.c_double, C.c_double, C.c_int, C.c_double]),
     ("rxmd_hip_get_barostat", C.c_int, [H, PD, PD, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
+    ("rxmd_hip_set_qeq_precision", C.c_int, [H, C.c_int]),
+    ("rxmd_hip_get_qeq_precision", C.c_int, [H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("rxmd_hip_QEq", C.c_int, [H, C.c_int, C.c_int, PD, PD, PD]),
     ("rxmd_hip_FORCE", C.c_int, [H, C.c_int, C.c_int, PD, PD, PD, PD, PD]),
     ("rxmd_hip_get_stats", C.c_int, [H, C.POINTER(RxmdStats)]),

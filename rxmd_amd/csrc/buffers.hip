@@ -167,6 +167,7 @@ void Engine::declare_buffers() {
   b.add(win_gint, G_WIN, Dim::Cap, 1, 0, P, whole);
   b.add(win_gbnd, G_WIN, Dim::Cap, 1, 0, P, whole);
   b.add(sl10, G_LIST10, Dim::List10, 1, 0, P, whole);
+  b.add(hess32, G_LIST10, Dim::List10, 1, 0, P, whole, BUF_QEQ_F32);      // the matrix values as REAL(4), only while set_qeq_precision(32) is in force
   b.add(partials, G_PARTIALS, Dim::Cap, 1, 1024, P, whole);   // + the 128 x 4 first-level sums of k_reduce_fused, behind the per-workgroup partials at a fixed offset
   b.add(scal, G_SETUP, Dim::Fixed, 0, SCAL_N, Z, never, res);
   b.add_pinned(h_scal, G_SETUP, H_SCAL_DOUBLES, true);        // coherent: the update kernel's tail stores the CG snapshot into it and the host polls it
@@ -204,6 +205,7 @@ size_t Buffers::count(const Buf &b, const Engine &e) const {
 
 void Buffers::alloc_one(Buf &b, const Engine &e) {
   if ((b.flags & BUF_PQEQ) && !e.ff.pqeq) return;
+  if ((b.flags & BUF_QEQ_F32) && e.qeq_bits_req != 32) return;
   const size_t bytes = count(b, e) * b.elem;
   *b.pp = b.space == Space::Device ? dev_alloc(bytes, b.fill) : pinned_alloc(bytes, b.space == Space::PinnedCoherent);
   b.bytes = bytes;

@@ -270,6 +270,17 @@ int rxmd_hip_get_barostat(rxmd_handle h, double p6_GPa[6], double mu[3], double 
   });
 }
 
+// ---- mixed-precision charge solver: width of the matrix value stream of the QEq window pass ----
+int rxmd_hip_set_qeq_precision(rxmd_handle h, int matrix_bits) {
+  return guarded(h, [&](Engine &e) { e.set_qeq_precision(matrix_bits); });
+}
+int rxmd_hip_get_qeq_precision(rxmd_handle h, int *requested_bits, int *in_use_bits) {
+  return guarded(h, [&](Engine &e) {
+    if (requested_bits) *requested_bits = e.qeq_bits_req;
+    if (in_use_bits) *in_use_bits = e.qeq_bits_used;
+  });
+}
+
 // ---- the reference's own argument shapes (QEq(atype,pos,q) qeq.F90:2 ; FORCE(atype,pos,f,q) pot.F90:2) ----
 static void upload_reference_arrays(Engine &e, int nbuffer, int natoms, const double *atype, const double *pos, const double *q) {
   if (natoms < 0 || (natoms == 0 && e.nprocs == 1) || nbuffer < natoms) throw EngineError(RXMD_E_ARG, "bad natoms/nbuffer");

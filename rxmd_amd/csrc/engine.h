@@ -168,7 +168,7 @@ enum class Refill : unsigned char { Never, Whole, Ghosts };          // RXMD_POI
 enum class Space : unsigned char { Device, Pinned, PinnedCoherent };
 // re-allocation groups.  Those before G_ON_DEMAND exist from set-up on (Buffers::alloc_setup); the others are allocated when first needed
 enum { G_SETUP, G_BOND, G_WIN, G_CELLSTART, G_LIST10, G_PARTIALS, G_ON_DEMAND, G_CUBTMP = G_ON_DEMAND, G_FFBLOB, G_PQBLOB, G_E4B, G_SEG, G_SEG_PINNED, G_XBUF, G_DH_SERVE, G_COUNT };
-enum : unsigned { BUF_PQEQ = 1u, BUF_RESIDENT = 2u };                // exists only with PQEq ; resident state that grow_capacity carries over
+enum : unsigned { BUF_PQEQ = 1u, BUF_RESIDENT = 2u, BUF_QEQ_F32 = 4u };   // exists only with PQEq ; resident state that grow_capacity carries over ; exists only while the fp32 matrix stream is requested (set_qeq_precision)
 struct Buf { void **pp; size_t elem; int group; Dim dim; size_t mul, add_; Fill fill; Refill refill; unsigned flags; Space space; size_t bytes; };   // bytes: what was allocated (0: nothing of ours)
 struct Buffers {
   std::vector<Buf> v;
@@ -274,6 +274,13 @@ struct Engine {
   double *cds = nullptr, *cd = nullptr, *cc_ = nullptr;
   // 10 A list
   int *nb10 = nullptr, *n10 = nullptr; double *hess = nullptr;
+  // Mixed-precision charge solver (rxmd_hip_set_qeq_precision; plain QEq only): with 32 requested the list sweep rounds every matrix value ONCE to
+  // REAL(4) and writes it to both streams -- hess (double: row pass, debug tap 7) and hess32 (float: the fp32 instance of the window pass, 6 instead
+  // of 10 bytes per entry) -- and forms its row sums of the start vector from the rounded value: one operator on every path.  Products, sums,
+  // vectors and scalars stay double.  qeq_bits_used: width of the value stream the last matrix pass read.
+  float *hess32 = nullptr;
+  int qeq_bits_req = 64, qeq_bits_used = 64;
+  void set_qeq_precision(int bits);
   size_t partials_cap = 0;
   // reductions
   double *partials = nullptr;  // [nblocks_red * 16]

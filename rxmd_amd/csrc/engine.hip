@@ -93,6 +93,7 @@ Engine::Engine(const rxmd_config &c) : cfg(c) {
   spin_wait = opt.spin_wait != 0;
   halo_direct = opt.halo_direct;
   comm_timeout_s = opt.comm_timeout_s;
+  if (opt.qeq_f32 != 0 && !ff.pqeq) qeq_bits_req = 32;      // (RXMD_QEQ_F32=1; PQEq carries a second value stream and stays at 64)
   MAXNB = cfg.maxneighbs > 0 ? cfg.maxneighbs : 30;
   if (MAXNB > 31) throw EngineError(RXMD_E_ARG, "maxneighbs must be <= 31 (the wavefront-per-centre kernels stage the bond slots of two atoms in one 64-lane wavefront; the reference uses 30)");
   int ndev = 0;
@@ -1549,6 +1550,22 @@ void Engine::build_ghosts_and_lists(bool qeq_prepass) {
   collect_timers();
   outer_end(t_lists);
   pq_matrix_stale = false;
+}
+
+// Width of the matrix value stream of the QEq window pass (rxmd_hip_set_qeq_precision): 64 = the default path, 32 = values rounded once to
+// REAL(4) in the list sweep and streamed as float.  Takes effect at the next QEq call: the lists are invalidated and the G_LIST10 group is
+// allocated again, with or without hess32, as the stride growth of build_ghosts_and_lists does.
+void Engine::set_qeq_precision(int bits) {
+  if (bits != 64 && bits != 32) throw EngineError(RXMD_E_ARG, "matrix_bits must be 64 or 32");
+  if (bits == 32 && ff.pqeq) throw EngineError(RXMD_E_ARG, "the fp32 matrix stream is not available with PQEq (it carries a second value stream)");
+  if (bits == qeq_bits_req) return;
+  qeq_bits_req = bits;
+  lists_valid = false;
+  if (hess) {                                        // (the group exists once the atoms are set)
+    sync_stream();
+    bufs.free_group(G_LIST10); bufs.alloc_group(*this, G_LIST10);
+    nb10_valid = false;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -261,7 +261,11 @@ __global__ void __launch_bounds__(32 * WIN_ROWS) k_win_columns(int N, Grid g, co
 
 constexpr int L10_ROWS = 8;      // rows (wavefronts) of a workgroup of the 10 A sweep: half a window group
 constexpr int L10_CAP = 1600;    // staged candidate positions of a workgroup (28 B each: 44.8 KB + 8 KB of queues and tables = three workgroups per CU; RDX: ~1,500 per 8 rows)
-template <bool SELFCHECK, bool PQ, bool ORTHO>
+// F32 (plain QEq with the fp32 matrix stream requested, Engine::set_qeq_precision): the interpolated value is rounded ONCE to REAL(4) and that
+// value goes everywhere -- the float stream hess32 of the fp32 window pass, the double stream hess (row pass, debug tap 7) and the row sums of
+// the CG start vector below -- so that every form of the matrix pass applies the same operator and the gradient recurrence of qeq_mode 1
+// starts from a vector of the matrix it iterates with.
+template <bool SELFCHECK, bool PQ, bool ORTHO, bool F32 = false>
 __global__ void __launch_bounds__(64 * L10_ROWS) k_list10(int N, int S10, Grid g, RefMesh rm, DevFF ff, const int *__restrict__ cellid, const int *__restrict__ cellstart,
                                                  const double4 *__restrict__ sorted,
                                                  const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
@@ -271,7 +275,8 @@ __global__ void __launch_bounds__(64 * L10_ROWS) k_list10(int N, int S10, Grid g
                                                  const double4 *__restrict__ sorted_shl, const double *__restrict__ shx, const double *__restrict__ shy, const double *__restrict__ shz,
                                                  double *__restrict__ hsc, double4 *__restrict__ pqrow,
                                                  const double2 *__restrict__ xs0, double2 *__restrict__ s_all, double2 *__restrict__ s_gh, int *__restrict__ rowflag,
-                                                 const int *__restrict__ rows_sorted, unsigned short *__restrict__ sl10, const int *__restrict__ rowcols, const int *__restrict__ grp_base, int *__restrict__ gflag) {
+                                                 const int *__restrict__ rows_sorted, unsigned short *__restrict__ sl10, const int *__restrict__ rowcols, const int *__restrict__ grp_base, int *__restrict__ gflag,
+                                                 float *__restrict__ hess32 = nullptr) {
   __shared__ int s_q[L10_ROWS][128];     // accepted candidates: (stencil column of the row << 20 | candidate number in the row): position, atom, type and distance come back from the staged copy
   __shared__ int s_K[L10_ROWS][32], s_E[L10_ROWS][32], s_L[L10_ROWS][32];  // per stencil column of a row: first sorted position of its run - candidates before it / slot base of the column in the group's window / the same as s_K for the staged copy
   __shared__ int s_ix2[256];             // inxn2 row of the row's type would do; the whole (n1 x n1) table is 64-256 words
@@ -370,6 +375,7 @@ __global__ void __launch_bounds__(64 * L10_ROWS) k_list10(int N, int S10, Grid g
           drtb = drtb * ff.UDRi;
           const double2 T = ff.tabQEq2[static_cast<size_t>(inxn) * (NTABLE + 2) + itb];        // (T[itb], T[itb + 1]) in one 16-byte load
           h = (1.0 - drtb) * T.x + drtb * T.y;
+          if (F32) h = static_cast<double>(static_cast<float>(h));     // the one rounding of the fp32 matrix stream
         }
         {   // window slot: the candidate's column (of this row) -> the group's table entry -> first unit of the column + offset inside it
 #ifdef RXMD_EXPERIMENTS
@@ -395,6 +401,7 @@ __global__ void __launch_bounds__(64 * L10_ROWS) k_list10(int N, int S10, Grid g
         if (!(g.probe & 16))
 #endif
         __builtin_nontemporal_store(h, hess + row + slot);
+        if (F32) __builtin_nontemporal_store(static_cast<float>(h), hess32 + row + slot);
       }
     }
     cnt += nproc;
@@ -505,7 +512,7 @@ __global__ void __launch_bounds__(64 * L10_ROWS) k_list10(int N, int S10, Grid g
   if (qn > 0) emit(qn);
   if (live) {
   if (cnt > S10) { if (lane == 0) { atomicMax(&err[1], cnt); atomicCAS(&err[0], DERR_NONE, DERR_MAXN10); } cnt = S10; }  // qeq.F90:248-252
-  if (lane < 4 && cnt + lane < ((cnt + 3) & ~3)) { if (nb10) nb10[row + cnt + lane] = 0; hess[row + cnt + lane] = 0.0; sl10[row + cnt + lane] = 0; }   // zero-pad the row to a multiple of 4 (value 0, slot 0)
+  if (lane < 4 && cnt + lane < ((cnt + 3) & ~3)) { if (nb10) nb10[row + cnt + lane] = 0; hess[row + cnt + lane] = 0.0; sl10[row + cnt + lane] = 0; if (F32) hess32[row + cnt + lane] = 0.0f; }   // zero-pad the row to a multiple of 4 (value 0, slot 0)
   if (xs0) {
     ra = wave_sum_l(ra); rg = wave_sum_l(rg);
     if (lane == 0) { s_all[i] = make_double2(ra, 0.0); s_gh[i] = make_double2(rg, 0.0); }
@@ -645,10 +652,12 @@ void Engine::build_list10() {
   int *const nb10_w = needs_nb10(selfcheck) ? nb10 : nullptr;       // (win_valid: still the previous build's)
   nb10_valid = nb10_w != nullptr;
 #define RX_LIST10(SC, PQF) do { if (grid.ortho) RX_LIST10_O(SC, PQF, true); else RX_LIST10_O(SC, PQF, false); } while (0)
-#define RX_LIST10_O(SC, PQF, OR)                                                                                                               \
-  k_list10<SC, PQF, OR><<<std::max(win_groups, 1) * (WIN_ROWS / L10_ROWS_LAUNCH), 64 * L10_ROWS_LAUNCH, 0, stream>>>(N, S10, grid, rmesh, dff, cellid, cellstart, sorted_xyzi, pos[0], pos[1], pos[2], spos[0], spos[1], spos[2], type, gid, \
+#define RX_LIST10_O(SC, PQF, OR) do { if (!PQF && f32) RX_LIST10_F(SC, false, OR, true); else RX_LIST10_F(SC, PQF, OR, false); } while (0)
+#define RX_LIST10_F(SC, PQF, OR, F)                                                                                                            \
+  k_list10<SC, PQF, OR, F><<<std::max(win_groups, 1) * (WIN_ROWS / L10_ROWS_LAUNCH), 64 * L10_ROWS_LAUNCH, 0, stream>>>(N, S10, grid, rmesh, dff, cellid, cellstart, sorted_xyzi, pos[0], pos[1], pos[2], spos[0], spos[1], spos[2], type, gid, \
                                                     nb10_w, hess, n10, d_err, sorted_shl, shl[0], shl[1], shl[2], hsc, pqrow, sums_from_list ? xs : nullptr, sall, sgh, multi() ? flags : nullptr, \
-                                                    rows_sorted, sl10, rowcols, grp_base, gflag)
+                                                    rows_sorted, sl10, rowcols, grp_base, gflag, F ? hess32 : nullptr)
+  const bool f32 = qeq_bits_req == 32 && !ff.pqeq && hess32 != nullptr;   // the values of this build are rounded to REAL(4), in both streams
   win_valid = false;
   build_windows();
   int *gflag = win_flag;
@@ -660,6 +669,7 @@ void Engine::build_list10() {
   kt_end(kt10);
 #undef RX_LIST10
 #undef RX_LIST10_O
+#undef RX_LIST10_F
   if (multi()) {                                     // interior groups (no row with a ghost partner) / boundary groups: the two launches of an overlapped pass
     size_t tb = cubtmp_bytes;
     RX_HIP(hipcub::DeviceScan::ExclusiveSum(cubtmp, tb, win_flag, scanout2, win_groups + 1, stream));

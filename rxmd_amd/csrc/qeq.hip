@@ -387,6 +387,7 @@ void Engine::allreduce_scal4(int n) {
 // One-time cost ~35 ms per placement, +6.3 GB of memory while a candidate is alive (979,776 atoms).  Measured, fresh processes alternating on one
 // box, default bench: 52.4-54.1 ms/step with the search against 53.4-55.6 without (the pass in the loop follows the kept placement + 0.03-0.04 ms).
 void Engine::tune_window_placement() {
+  if (qeq_bits_req == 32) return;                   // the search times and moves the double streams; with the fp32 value stream requested there is none (place_draws stays 0), and a later return to 64 may still search
   place_tuned = true;
   const int tries = static_cast<int>(opt.place_tries);       // (round 4: the draws of one box lie between 0.80 and 0.93 ms, a third of them fast: ten draws miss the fast kind in 3 % of the processes, six in 12 %)
   if (tries <= 1 || !win_valid || N < 65536) return;              // (small systems: nothing to gain)
@@ -628,22 +629,30 @@ void Engine::qeq() {
       const bool one_trip = !ff.pqeq && opt.spmv_one_trip != 0 && max_row10 > 256 && max_row10 <= 384;      // (PQEq: the third stream of 384 entries does not fit the 64 registers of two workgroups per CU)
       const bool pq_pre = ff.pqeq && opt.pq_prefetch != 0;
       st.spmv_nstep = pq_pre ? 1 : (one_trip ? 3 : 2); st.spmv_var = pq_pre ? WIN_PREFETCH : (one_trip ? WIN_LEAN : (WIN_PREFETCH | WIN_LEAN));   // what the line below dispatches (bench.py names the instance whose counters it quotes)
+      // fp32 matrix stream (set_qeq_precision(32), plain QEq): the float instance in the default form, whatever RXMD_SPMV_ONE_TRIP says; a row's first float is
+      // 16-byte aligned because S10 is a multiple of 64 (256 bytes per row stride), checked all the same
+      const bool f32 = qeq_bits_req == 32 && !ff.pqeq && hess32 != nullptr && (S10 & 3) == 0;
+      qeq_bits_used = f32 ? 32 : 64;
+      if (f32) { st.spmv_nstep = 2; st.spmv_var = WIN_PREFETCH | WIN_LEAN; }
       // per-row operands of the tail: by atom, or (run-ahead loop in row order, MODE_HSH only) by the row's place in rows_sorted
       const int *p_n10 = pass_roword ? r_n10 : n10, *p_type = pass_roword ? r_type : type;
       const double2 *p_hst = pass_roword ? r_hst : hst; double2 *p_gst = pass_roword ? r_gst : gst;
 #define RX_WIN3(M, S, P) do { if (P && pq_pre) k_spmv_win<M, S, P, 1, WIN_PREFETCH><<<ng, 64 * WIN_ROWS, lds, stream>>>(N, G, S10, dff, sl10, hess, p_n10, rows_sorted, win_k, win_cnt, xs, p_hst, p_gst, qst, q, p_type, scal, partials, ra, rg, hsc, pqrow, glist, ng, pbase, stopflag, win_flag, pass_roword ? 1 : 0); \
                               else if (one_trip && !P) k_spmv_win<M, S, false, 3, WIN_LEAN><<<ng, 64 * WIN_ROWS, lds, stream>>>(N, G, S10, dff, sl10, hess, p_n10, rows_sorted, win_k, win_cnt, xs, p_hst, p_gst, qst, q, p_type, scal, partials, ra, rg, hsc, pqrow, glist, ng, pbase, stopflag, win_flag, pass_roword ? 1 : 0); \
                               else k_spmv_win<M, S, P, 2, WIN_PREFETCH | WIN_LEAN><<<ng, 64 * WIN_ROWS, lds, stream>>>(N, G, S10, dff, sl10, hess, p_n10, rows_sorted, win_k, win_cnt, xs, p_hst, p_gst, qst, q, p_type, scal, partials, ra, rg, hsc, pqrow, glist, ng, pbase, stopflag, win_flag, pass_roword ? 1 : 0); } while (0)
-#define RX_WIN(M, S) do { if (ff.pqeq) RX_WIN3(M, S, true); else RX_WIN3(M, S, false); } while (0)
+#define RX_WIN32(M, S) k_spmv_win<M, S, false, 2, WIN_PREFETCH | WIN_LEAN, float><<<ng, 64 * WIN_ROWS, lds, stream>>>(N, G, S10, dff, sl10, hess32, p_n10, rows_sorted, win_k, win_cnt, xs, p_hst, p_gst, qst, q, p_type, scal, partials, ra, rg, hsc, pqrow, glist, ng, pbase, stopflag, win_flag, pass_roword ? 1 : 0)
+#define RX_WIN(M, S) do { if (f32) RX_WIN32(M, S); else if (ff.pqeq) RX_WIN3(M, S, true); else RX_WIN3(M, S, false); } while (0)
       if (mode == MODE_HSH) { if (store) RX_WIN(MODE_HSH, true); else RX_WIN(MODE_HSH, false); }
       else { if (store) RX_WIN(MODE_GRAD, true); else RX_WIN(MODE_GRAD, false); }
 #undef RX_WIN
+#undef RX_WIN32
 #undef RX_WIN3
       return ng;
     }
     const int rbl = rowlist ? nblk(nrows, SPMV_WPB) : rb;
     if (rbl == 0) return 0;
     st.spmv_nstep = 0; st.spmv_var = 0;
+    qeq_bits_used = 64;                          // (with 32 requested: the double stream holds the same rounded values)
     require_nb10();                              // the row form reads the 4-byte entries
 #define RX_PASS3(M, S, P, PI) k_spmv<M, S, P, PI><<<rbl, 64 * SPMV_WPB, 0, stream>>>(N, S10, dff, nb10, hess, n10, xs, hst, gst, qst, q, type, scal, partials, ra, rg, hsc, pqrow, swz, rowlist, nrows, pbase, stopflag)
 #define RX_PASS(M, S)                                                                                                  \
@@ -778,7 +787,7 @@ void Engine::qeq() {
     // No host wait here (round 5): the kernels of the iteration that did not happen are still in the queue (they return at once and store no snapshot)
     // and FORCE queues behind them in stream order.  (Until round 5 a sync here cost ~50 us of idle GPU per step.)
     outer_end(t_qeq);
-    if (!place_tuned && win_used && it >= 1) { sync_stream(); collect_timers(); tune_window_placement(); }
+    if (!place_tuned && win_used && it >= 1 && qeq_bits_req != 32) { sync_stream(); collect_timers(); tune_window_placement(); }
     return;
   }
   for (it = 0; it <= nmax - 1; ++it) {
@@ -876,7 +885,7 @@ void Engine::qeq() {
   nstep_qeq = it; last_est = Est;
   st.qeq_iters_last = it; st.qeq_iters_total += it; st.qeq_calls += 1; qeq_iters_smooth = qeq_iters_smooth < 0.0 ? it : 0.75 * qeq_iters_smooth + 0.25 * it;
   outer_end(t_qeq);
-  if (!place_tuned && win_used && it >= 1) { sync_stream(); collect_timers(); tune_window_placement(); }
+  if (!place_tuned && win_used && it >= 1 && qeq_bits_req != 32) { sync_stream(); collect_timers(); tune_window_placement(); }
 }
 
 }  // namespace rxmd

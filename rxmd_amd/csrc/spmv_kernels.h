@@ -168,10 +168,18 @@ __global__ void __launch_bounds__(1024) k_spmv(int N, int S10, DevFF ff, const i
 // back to back in one process, NOTES.md 3.  Variants are compared compiled side by side through VAR and debug tap 104.)
 // FORM (bit set): WIN_PREFETCH = the second batch of a row is requested before the workgroup's barrier; WIN_LEAN = groups without a ghost partner skip the
 // ghost-column sums; WIN_RANKROWS = experiments build only.  Plain QEq runs WIN_PREFETCH | WIN_LEAN (RXMD_SPMV_ONE_TRIP=1 and rows of 257-384 entries: NSTEP 3, WIN_LEAN), PQEq NSTEP 1 with WIN_PREFETCH (RXMD_PQ_PREFETCH=0: NSTEP 2, no prefetch).
+// VT (value type of the matrix stream): double, or float for the mixed-precision solver (Engine::set_qeq_precision(32), plain QEq, NSTEP 2, WIN_PREFETCH |
+// WIN_LEAN only): the values were rounded once to REAL(4) by the list sweep and arrive as float pairs -- 8 bytes per lane and request, 6 instead of 10
+// bytes per entry with the slot -- sit in the register sets as floats and are widened where they are used; window, slots, products, sums, tail and
+// partial sums are those of the double instance.  The double instances are the same code with or without this parameter
+// (profiles/qeq_f32_resource_usage_parent_vs_change.txt).
 [[maybe_unused]] constexpr int WIN_RANKROWS = 1;
 constexpr int WIN_PREFETCH = 2, WIN_LEAN = 4;
-template <int MODE, bool STORE, bool PQ, int NSTEP = 2, int VAR = 0>      // VAR = FORM bits; VAR & 2: the second batch of a row is requested before the workgroup's barrier (below); VAR & 4: groups without a ghost partner skip the ghost-column sums (below); the default of plain QEq is 6.  NSTEP x 128 entries of a row in flight per register set (2; 3 = every row of at most 384 entries is one trip, the choice for water in rounds 4-5 -- 1.478 against 1.529 ms then, 1.61 against 1.58 since round 6, no longer the default; 1 for PQEq, whose third stream doubles a set); VAR: variants under measurement, compiled side by side and timed by debug tap 104
-__global__ void __launch_bounds__(64 * WIN_ROWS, 8) k_spmv_win(int N, int G, int S10, DevFF ff, const unsigned short *__restrict__ sl10, const double *__restrict__ hess, const int *__restrict__ n10,
+template <class VT> struct WinVal;
+template <> struct WinVal<double> { typedef double2 pair; static __device__ inline pair make(double a, double b) { return make_double2(a, b); } };
+template <> struct WinVal<float> { typedef float2 pair; static __device__ inline pair make(float a, float b) { return make_float2(a, b); } };
+template <int MODE, bool STORE, bool PQ, int NSTEP = 2, int VAR = 0, class VT = double>      // VAR = FORM bits; VAR & 2: the second batch of a row is requested before the workgroup's barrier (below); VAR & 4: groups without a ghost partner skip the ghost-column sums (below); the default of plain QEq is 6.  NSTEP x 128 entries of a row in flight per register set (2; 3 = every row of at most 384 entries is one trip, the choice for water in rounds 4-5 -- 1.478 against 1.529 ms then, 1.61 against 1.58 since round 6, no longer the default; 1 for PQEq, whose third stream doubles a set); VAR: variants under measurement, compiled side by side and timed by debug tap 104
+__global__ void __launch_bounds__(64 * WIN_ROWS, 8) k_spmv_win(int N, int G, int S10, DevFF ff, const unsigned short *__restrict__ sl10, const VT *__restrict__ hess, const int *__restrict__ n10,
                                                             const int *__restrict__ rows_sorted, const int *__restrict__ win_k, const int *__restrict__ win_cnt,
                                                             const double2 *__restrict__ xv, const double2 *__restrict__ hst, double2 *__restrict__ gst,
                                                             const double2 *__restrict__ qst, const double *__restrict__ q, const int *__restrict__ type,
@@ -190,6 +198,9 @@ __global__ void __launch_bounds__(64 * WIN_ROWS, 8) k_spmv_win(int N, int G, int
   constexpr int STEPS = NSTEP;
   constexpr int NT = 64 * WIN_ROWS;
   typedef double d2v __attribute__((ext_vector_type(2)));
+  typedef VT h2v __attribute__((ext_vector_type(2)));
+  typedef typename WinVal<VT>::pair hpair;
+  static_assert(std::is_same<VT, double>::value || (!PQ && NSTEP == 2), "the float value stream: plain QEq, two batches per register set");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
   const int gidx = xcd_swizzle(blockIdx.x, gridDim.x);
@@ -209,8 +220,8 @@ __global__ void __launch_bounds__(64 * WIN_ROWS, 8) k_spmv_win(int N, int G, int
 #else
   const size_t base = static_cast<size_t>(live ? row : 0) * S10;
 #endif
-  const d2v *hv2 = reinterpret_cast<const d2v *>(hess + base);
-  const d2v *cv2 = reinterpret_cast<const d2v *>((PQ ? hsc : hess) + base);
+  const h2v *hv2 = reinterpret_cast<const h2v *>(hess + base);
+  const d2v *cv2 = reinterpret_cast<const d2v *>(PQ ? hsc + base : nullptr);
   const unsigned *sl2 = reinterpret_cast<const unsigned *>(sl10 + base);
   // VAR & 4: a group none of whose rows has a ghost partner (gflags[grp] == 0: three groups in four of a large domain) takes a body WITHOUT the
   // ghost-column sums -- two selects and four FMAs of the twelve vector instructions per pair of entries, and two of the four reductions.  The flag
@@ -220,13 +231,13 @@ __global__ void __launch_bounds__(64 * WIN_ROWS, 8) k_spmv_win(int N, int G, int
   const bool gh = !((VAR & WIN_LEAN) != 0 && !PQ && gflags != nullptr) || gflags[grp] != 0;
   auto whole = [&](auto ghc) {
   constexpr bool GHC = decltype(ghc)::value;
-  double2 v[STEPS], c[STEPS]; unsigned ss[STEPS];
+  hpair v[STEPS]; double2 c[STEPS]; unsigned ss[STEPS];
   auto request = [&](int kb, int bound) {          // entries kb + 128 u + 2 lane and the next one
 #pragma unroll
     for (int u = 0; u < STEPS; ++u) {
       const int k = kb + 128 * u + 2 * lane;
       const bool ok = k < bound;
-      if (ok) { const d2v t2 = __builtin_nontemporal_load(hv2 + (k >> 1)); v[u] = make_double2(t2.x, t2.y); } else v[u] = make_double2(0.0, 0.0);
+      if (ok) { const h2v t2 = __builtin_nontemporal_load(hv2 + (k >> 1)); v[u] = WinVal<VT>::make(t2.x, t2.y); } else v[u] = WinVal<VT>::make(0.0, 0.0);
       ss[u] = ok ? __builtin_nontemporal_load(sl2 + (k >> 1)) : 0u;
       if (PQ && (MODE == MODE_GRAD || STORE)) { if (ok) { const d2v t2 = __builtin_nontemporal_load(cv2 + (k >> 1)); c[u] = make_double2(t2.x, t2.y); } else c[u] = make_double2(0.0, 0.0); }
     }
@@ -250,8 +261,8 @@ __global__ void __launch_bounds__(64 * WIN_ROWS, 8) k_spmv_win(int N, int G, int
 #pragma unroll
   for (int u = 0; u < STEPS; ++u) {                // entries behind the row's end: weight 0, slot 0
     const int k = 128 * u + 2 * lane;
-    if (k >= n) { v[u].x = 0.0; ss[u] &= 0xffff0000u; if (PQ) c[u].x = 0.0; }
-    if (k + 1 >= n) { v[u].y = 0.0; ss[u] &= 0x0000ffffu; if (PQ) c[u].y = 0.0; }
+    if (k >= n) { v[u].x = static_cast<VT>(0.0); ss[u] &= 0xffff0000u; if (PQ) c[u].x = 0.0; }
+    if (k + 1 >= n) { v[u].y = static_cast<VT>(0.0); ss[u] &= 0x0000ffffu; if (PQ) c[u].y = 0.0; }
   }
   // VAR & 2 (plain QEq): the row's NEXT batch is requested before the barrier, behind the window's data (a wavefront's loads return in order:
   // the window does not wait for it) -- the round trip of the second batch runs under the barrier and the first batch's arithmetic instead of
@@ -259,13 +270,13 @@ __global__ void __launch_bounds__(64 * WIN_ROWS, 8) k_spmv_win(int N, int G, int
   // PQEq takes the prefetch form with ONE batch of 128 entries per register set (NSTEP 1): its third stream (the shell-core values) doubles the registers of a
   // set, and two sets of two batches do not fit the 64 registers of eight workgroups per CU
   constexpr bool PRE = (VAR & WIN_PREFETCH) != 0 && (!PQ || NSTEP == 1);
-  double2 vn[STEPS], cn[STEPS]; unsigned sn[STEPS];
+  hpair vn[STEPS]; double2 cn[STEPS]; unsigned sn[STEPS];
   auto request_next = [&](int kb) {
 #pragma unroll
     for (int u = 0; u < STEPS; ++u) {
       const int k = kb + 128 * u + 2 * lane;
       const bool ok = k < n;
-      if (ok) { const d2v t2 = __builtin_nontemporal_load(hv2 + (k >> 1)); vn[u] = make_double2(t2.x, t2.y); } else vn[u] = make_double2(0.0, 0.0);
+      if (ok) { const h2v t2 = __builtin_nontemporal_load(hv2 + (k >> 1)); vn[u] = WinVal<VT>::make(t2.x, t2.y); } else vn[u] = WinVal<VT>::make(0.0, 0.0);
       sn[u] = ok ? __builtin_nontemporal_load(sl2 + (k >> 1)) : 0u;
       if (PQ && (MODE == MODE_GRAD || STORE)) { if (ok) { const d2v t2 = __builtin_nontemporal_load(cv2 + (k >> 1)); cn[u] = make_double2(t2.x, t2.y); } else cn[u] = make_double2(0.0, 0.0); }
     }
@@ -273,13 +284,14 @@ __global__ void __launch_bounds__(64 * WIN_ROWS, 8) k_spmv_win(int N, int G, int
   if (PRE && n > 128 * STEPS) request_next(128 * STEPS);
   __syncthreads();
   double as = 0.0, at = 0.0, gs_ = 0.0, gt_ = 0.0;
-    auto batch = [&](const double2 (&vv)[STEPS], const unsigned (&sv)[STEPS], const double2 (&cv)[STEPS]) {      // one batch of 128 x STEPS entries out of registers and the LDS window
+    auto batch = [&](const hpair (&vv)[STEPS], const unsigned (&sv)[STEPS], const double2 (&cv)[STEPS]) {      // one batch of 128 x STEPS entries out of registers and the LDS window
 #pragma unroll
       for (int u = 0; u < STEPS; ++u) {
         const double2 y0 = s_x[sv[u] & 0x7fffu], y1 = s_x[(sv[u] >> 16) & 0x7fffu];
-        as += vv[u].x * y0.x; at += vv[u].x * y0.y; as += vv[u].y * y1.x; at += vv[u].y * y1.y;
+        const double hx = vv[u].x, hy = vv[u].y;                    // (float stream: widened here, exactly)
+        as += hx * y0.x; at += hx * y0.y; as += hy * y1.x; at += hy * y1.y;
         if (GHC && (MODE == MODE_GRAD || STORE) && !PQ) {
-          const double g0 = (sv[u] & 0x8000u) ? vv[u].x : 0.0, g1 = (sv[u] & 0x80000000u) ? vv[u].y : 0.0;     // select the weight, not the sums
+          const double g0 = (sv[u] & 0x8000u) ? hx : 0.0, g1 = (sv[u] & 0x80000000u) ? hy : 0.0;     // select the weight, not the sums
           gs_ += g0 * y0.x; gt_ += g0 * y0.y; gs_ += g1 * y1.x; gt_ += g1 * y1.y;
         }
         if ((MODE == MODE_GRAD || STORE) && PQ) { gs_ += cv[u].x * y0.x; gt_ += cv[u].x * y0.y; gs_ += cv[u].y * y1.x; gt_ += cv[u].y * y1.y; }

@@ -80,6 +80,17 @@ class RxmdEngine:
         self._chk(self.L.rxmd_hip_get_barostat(self.h, _ptr(p6), _ptr(mu), C.byref(vol), C.byref(n)))
         return dict(p6=p6, mu=mu, volume=vol.value, couplings=n.value)
 
+    def set_qeq_precision(self, bits):
+        """width of the QEq matrix value stream: 64 (default) or 32 = values rounded once to REAL(4) and streamed as float by the window pass, all
+        arithmetic in double (plain QEq only; RxmdError RXMD_E_ARG otherwise).  Takes effect at the next QEq call."""
+        self._chk(self.L.rxmd_hip_set_qeq_precision(self.h, int(bits)))
+
+    def qeq_precision(self):
+        """(requested, in_use): in_use is the width of the value stream the last matrix pass read, 32 only when the float window instance ran"""
+        req = C.c_int(0); use = C.c_int(0)
+        self._chk(self.L.rxmd_hip_get_qeq_precision(self.h, C.byref(req), C.byref(use)))
+        return req.value, use.value
+
     def close(self):
         if getattr(self, "h", None):
             self.L.rxmd_hip_destroy(self.h); self.h = None
