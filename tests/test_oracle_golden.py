@@ -408,3 +408,25 @@ def test_bond_file_and_pdb_formatters_against_the_references_files():
         assert abs(float(x[54:60]) - float(y[54:60])) <= 1.01e-2
         same += x == y
     assert same >= 0.97 * n, same
+
+
+def test_off_lattice_systems_stay_in_their_regimes():
+    """The dense, dilute and shaken boxes of test_gpu_offlattice.py (offlattice_systems.py), built with the oracle alone: each must keep the property it
+    exists for -- bond lists longer than 15 / 24, 10 A rows longer than 512 / 1024 or shorter than 128, an atom without a bond -- and the box compressed
+    to 0.70 must run into the reference's MAXNEIGHBS trap (main.F90:402-407).  A change of the inputs or of the oracle that moves a case out of its
+    regime shows here, without a GPU."""
+    import offlattice_systems as ol
+    seen = {}
+    for name in ol.NAMES:
+        o = ol.oracle(name, isQEq=1, NMAXQEq=5, QEq_tol=1e-300)
+        assert o.qeq() == 5
+        o.force()
+        seen[name] = ol.regime(o)
+        ol.check_gates(name, seen[name])
+        assert np.isfinite(o.energy()).all() and np.isfinite(o.forces()).all()
+    assert seen["rdx-dense"]["natoms"] == 1344 and seen["ice-dense"]["natoms"] == 2304
+    assert seen["rdx-dense"]["max_nb"] <= 24 < seen["rdx-denser"]["max_nb"] <= 30       # the two sides of the angle kernel's 8 / 4 centres per wavefront
+    assert 12 < seen["rdx-shaken"]["max_nb"] <= 15 and 12 < seen["ice-dense"]["max_nb"] <= 15   # eight centres per wavefront, packed torsion instance
+    with pytest.raises(RuntimeError, match="overflow of max # in neighbor list"):
+        o = ol.oracle("rdx-trap", isQEq=1, NMAXQEq=5, QEq_tol=1e-300)
+        o.qeq(); o.force()
