@@ -383,7 +383,7 @@ struct Engine {
   void alloc_device();
   void free_device();
   void ghost_build();
-  void ghost_build_fused(); void migrate_fused(); void ensure_seg_buffers(int nblocks);   // single rank: the six-stage self exchange as 26 image segments (engine.hip)
+  void ghost_build_fused(); void migrate_fused(); void ensure_seg_buffers(int nblocks);   // single rank: the six-stage self exchange as 26 image segments (exchange.hip)
   // counts the host waits for, handed over through pinned host memory: word = sequence number << 32 | value; the host polls until every word carries the
   // sequence number of its request (rccl_comm.hip: pinned_wait) -- no copy, no stream synchronisation, and the kernels queued behind the producer keep running
   unsigned long long *h_pub = nullptr; unsigned pub_seq = 0u;
@@ -418,13 +418,19 @@ struct Engine {
   bool win_valid = false, win_used = false;    // win_used: the last matrix pass was a window pass
   void halo_refresh(double2 *v2, double *v1);       // QCOPY1/QCOPY2: ghosts <- owners (self exchange, resolved roots)
   void halo_staged(double *v, int ncomp);           // the same through the six-stage exchange (multi-rank)
-  long long exchange_stage(int d, bool reverse, long long nsend, long long known_nrecv = -1);  // one send_recv of comm.F90:291-364; returns #doubles received
-  void exchange_pair(int d0, bool reverse, long long n0, long long r0, long long n1, long long r1);  // stages d0 and d0+1 (one axis) in one round, counts known
-  void exchange_pair_sized(int d0, long long n0, long long n1, long long &r0, long long &r1);       // the same when the receive counts are not known yet (ghost build)
-  void rccl_exchange_pair_sized(int to0, int from0, long long n0, long long &r0, int to1, int from1, long long n1, long long &r1);
-  int *flags2 = nullptr, *scanout2 = nullptr;       // second stage of an axis pair (ghost build)
-  void rccl_exchange_pair(int to0, int from0, long long n0, long long r0, int to1, int from1, long long n1, long long r1);
-  bool stage_pairs = true;                          // RXMD_NO_STAGE_PAIRS=1: one round per stage as the reference does (six per halo)
+  // The six exchange stages are walked in rounds (exchange.hip): a round is one stage, or the + and - stage of an axis together.  Ghost build and
+  // migration pair when stage_pairs is set; vector halos and the force fold, whose receive counts are known, also need a transport that takes them.
+  struct Round { int d0, n; };                      // stages d0 .. d0 + n - 1, n = 1 or 2
+  bool stage_pairs = true;                          // RXMD_NO_STAGE_PAIRS=1: one round per stage as the reference does (six per walk)
+  bool known_counts_pair() const { return stage_pairs && (nccl || (has_comm && comm.exchange_known)); }
+  int *flags2 = nullptr, *scanout2 = nullptr;       // selection of the second stage of a round (flags / scanout: the first)
+  int *sel_flags(int k) const { return k ? flags2 : flags; }
+  int *sel_scan(int k) const { return k ? scanout2 : scanout; }
+  int stage_sends(int d) const { return sendoff[d + 1] - sendoff[d]; }     // atoms stage d sends / ghosts it received, as the last ghost build left them
+  int stage_ghosts(int d) const { return copyptr[d] - copyptr[d - 1]; }
+  void select_round(Round r, int nscan, double dr, int skip_dead, int total[2]);   // flags, scans and totals of the round's stages, one host wait
+  void exchange_round(Round r, bool reverse, const long long nsend[2], long long nrecv[2], bool counts_known);   // the send_recv of comm.F90:291-364 for every message of the round
+  void rccl_exchange_round(int n, const int to[2], const int from[2], const long long nsend[2], long long nrecv[2], bool counts_known);
   // Direct vector halo (RXMD_HALO_DIRECT=1): every ghost value comes straight from the rank that OWNS the atom, all peers in one grouped
   // exchange, instead of the reference's x -> y -> z forwarding (comm.F90:68-86: three dependent rounds per halo).  The ghost build carries
   // (owner rank, owner's local index) along with every atom; after it each rank asks its ghosts' owners for their index lists once.
@@ -446,7 +452,6 @@ struct Engine {
   void *nccl = nullptr; double *cnt_dev = nullptr, *cnt_host = nullptr; bool force_staged = false, force_remote = false;
   void rccl_init(const unsigned char id128[128], int rank, int world);
   void rccl_destroy();
-  long long rccl_exchange(int to, int from, long long nsend, long long known_nrecv);
   void rccl_allreduce_dev(double *dev, int n);
   // every host wait of the engine.  With a RCCL communicator attached a wait can depend on a peer that died or went another way (a
   // rank-local overflow, a mismatch of the exchange pattern): the wait is then a bounded poll -- RXMD_COMM_TIMEOUT_S seconds, default
@@ -457,8 +462,7 @@ struct Engine {
   bool spin_wait = true;
   void allreduce_scal4(int n = 4);                 // MPI_ALLREDUCE of scal[S_RAW0..n-1] (qeq.hip)
   void allreduce_host(double *buf, int n);         // the same for a host vector (setup paths)
-  void ghost_build_staged();
-  void migrate_staged();
+  void ghost_build_staged();                        // stage by stage: several ranks, or one rank under RXMD_NO_STAGE_PAIRS=1
   void sorted_copy(const double2 *v);               // QCOPY1/QCOPY2 fused with the cell-sorted gather copy -> xs
   void fold_ghost_forces();                         // CPBK
   void bond_orders();

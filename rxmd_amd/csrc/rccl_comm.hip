@@ -132,64 +132,40 @@ void Engine::rccl_destroy() {
   pinned_free(cnt_host); cnt_host = nullptr;
 }
 
-// one send_recv: nsend doubles of xbuf_send to `to`, the message of `from` into xbuf_recv; returns the doubles received
-long long Engine::rccl_exchange(int to, int from, long long nsend, long long known_nrecv) {
+// The n send_recv of one round in one group: message k of xbuf_send (back to back) to to[k], the message of from[k] into xbuf_recv.  Inside a
+// group: send 0, recv 0, send 1, recv 1 -- two messages to the same peer (an axis split in two: the + and the - neighbour are the same rank) are
+// matched in the order they were issued, which is the order the peer posts its receives in (its own first message first).
+// Receive counts not known (ghost build, migration): the size messages first, in one group (the reference sends the size inside MPI_Probe,
+// comm.F90:329-341), one host wait, then the payloads.
+void Engine::rccl_exchange_round(int n, const int to[2], const int from[2], const long long nsend[2], long long nrecv[2], bool counts_known) {
   ncclComm_t c = C(nccl);
-  long long nrecv = known_nrecv;
-  if (nrecv < 0) {                                        // size message first (the reference sends the size inside MPI_Probe, comm.F90:329-341)
-    cnt_host[0] = static_cast<double>(nsend);
-    RX_HIP(hipMemcpyAsync(cnt_dev, cnt_host, sizeof(double), hipMemcpyHostToDevice, stream));
+  if (!counts_known) {
+    for (int k = 0; k < n; ++k) cnt_host[k] = static_cast<double>(nsend[k]);
+    RX_HIP(hipMemcpyAsync(cnt_dev, cnt_host, n * sizeof(double), hipMemcpyHostToDevice, stream));
     RX_NCCL(ncclGroupStart());
-    RX_NCCL(ncclSend(cnt_dev, 1, ncclDouble, to, c, stream));
-    RX_NCCL(ncclRecv(cnt_dev + 1, 1, ncclDouble, from, c, stream));
+    for (int k = 0; k < n; ++k) {
+      RX_NCCL(ncclSend(cnt_dev + k, 1, ncclDouble, to[k], c, stream));
+      RX_NCCL(ncclRecv(cnt_dev + 2 + k, 1, ncclDouble, from[k], c, stream));
+    }
     RX_NCCL(ncclGroupEnd());
-    RX_HIP(hipMemcpyAsync(cnt_host + 1, cnt_dev + 1, sizeof(double), hipMemcpyDeviceToHost, stream));
+    RX_HIP(hipMemcpyAsync(cnt_host + 2, cnt_dev + 2, n * sizeof(double), hipMemcpyDeviceToHost, stream));
     sync_stream();
-    nrecv = static_cast<long long>(cnt_host[1]);
-    if (nrecv > static_cast<long long>(xbuf_doubles)) grow_xbuf_keep_send(static_cast<size_t>(nrecv), static_cast<size_t>(nsend));
+    for (int k = 0; k < n; ++k) nrecv[k] = static_cast<long long>(cnt_host[2 + k]);
   }
-  if (nsend > 0 || nrecv > 0) {
-    RX_NCCL(ncclGroupStart());
-    if (nsend > 0) RX_NCCL(ncclSend(xbuf_send, static_cast<size_t>(nsend), ncclDouble, to, c, stream));
-    if (nrecv > 0) RX_NCCL(ncclRecv(xbuf_recv, static_cast<size_t>(nrecv), ncclDouble, from, c, stream));
-    RX_NCCL(ncclGroupEnd());
-  }
-  return nrecv;
-}
-
-// both send_recv of one axis in one group: four point-to-point operations in flight at once.  Two messages to the same peer
-// (an axis split in two: the + and the - neighbour are the same rank) are matched in the order they were issued, which is the
-// order the peer posts its receives in (its own stage d0 message first).
-void Engine::rccl_exchange_pair(int to0, int from0, long long n0, long long r0, int to1, int from1, long long n1, long long r1) {
-  ncclComm_t c = C(nccl);
-  if (n0 + n1 + r0 + r1 == 0) return;
+  long long ns = 0, nr = 0;
+  for (int k = 0; k < n; ++k) { ns += nsend[k]; nr += nrecv[k]; }
+  if (!counts_known && nr > static_cast<long long>(xbuf_doubles)) grow_xbuf_keep_send(static_cast<size_t>(nr), static_cast<size_t>(ns));
+  if (ns + nr == 0) return;
   RX_NCCL(ncclGroupStart());
-  if (n0 > 0) RX_NCCL(ncclSend(xbuf_send, static_cast<size_t>(n0), ncclDouble, to0, c, stream));
-  if (r0 > 0) RX_NCCL(ncclRecv(xbuf_recv, static_cast<size_t>(r0), ncclDouble, from0, c, stream));
-  if (n1 > 0) RX_NCCL(ncclSend(xbuf_send + n0, static_cast<size_t>(n1), ncclDouble, to1, c, stream));
-  if (r1 > 0) RX_NCCL(ncclRecv(xbuf_recv + r0, static_cast<size_t>(r1), ncclDouble, from1, c, stream));
+  long long so = 0, ro = 0;
+  for (int k = 0; k < n; so += nsend[k], ro += nrecv[k], ++k) {
+    if (nsend[k] > 0) RX_NCCL(ncclSend(xbuf_send + so, static_cast<size_t>(nsend[k]), ncclDouble, to[k], c, stream));
+    if (nrecv[k] > 0) RX_NCCL(ncclRecv(xbuf_recv + ro, static_cast<size_t>(nrecv[k]), ncclDouble, from[k], c, stream));
+  }
   RX_NCCL(ncclGroupEnd());
 }
 
-// the pair with unknown receive counts: one group for the two size messages, one host wait, one group for the two payloads
-void Engine::rccl_exchange_pair_sized(int to0, int from0, long long n0, long long &r0, int to1, int from1, long long n1, long long &r1) {
-  ncclComm_t c = C(nccl);
-  cnt_host[0] = static_cast<double>(n0); cnt_host[1] = static_cast<double>(n1);
-  RX_HIP(hipMemcpyAsync(cnt_dev, cnt_host, 2 * sizeof(double), hipMemcpyHostToDevice, stream));
-  RX_NCCL(ncclGroupStart());
-  RX_NCCL(ncclSend(cnt_dev, 1, ncclDouble, to0, c, stream));
-  RX_NCCL(ncclRecv(cnt_dev + 2, 1, ncclDouble, from0, c, stream));
-  RX_NCCL(ncclSend(cnt_dev + 1, 1, ncclDouble, to1, c, stream));
-  RX_NCCL(ncclRecv(cnt_dev + 3, 1, ncclDouble, from1, c, stream));
-  RX_NCCL(ncclGroupEnd());
-  RX_HIP(hipMemcpyAsync(cnt_host + 2, cnt_dev + 2, 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
-  sync_stream();
-  r0 = static_cast<long long>(cnt_host[2]); r1 = static_cast<long long>(cnt_host[3]);
-  if (r0 + r1 > static_cast<long long>(xbuf_doubles)) grow_xbuf_keep_send(static_cast<size_t>(r0 + r1), static_cast<size_t>(n0 + n1));
-  rccl_exchange_pair(to0, from0, n0, r0, to1, from1, n1, r1);
-}
-
-// direct halo: one group with every peer (engine.hip: exchange_many); the rank's own segment only in the self-loop test mode
+// direct halo: one group with every peer (exchange.hip: exchange_many); the rank's own segment only in the self-loop test mode
 void Engine::rccl_exchange_many(const std::vector<long long> &soff, const std::vector<long long> &roff, int ncomp) {
   ncclComm_t c = C(nccl);
   const int np = (force_staged && nprocs == 1) ? 1 : nprocs;

@@ -40,6 +40,9 @@ def engine_rank(rank, world, port, case, vp, steps, out):
         lat_s, rec = system.geninit(ff, names, frac, lat, mc=mc, vprocs=vp, myid=rank)
         e = rxmd_amd.RxmdEngine(ff, lat_s, vprocs=vp, myid=rank, QEq_tol=1e-12, NMAXQEq=2000, device=0)
         tr = TorchTransport(mode="staged", device=torch.device("cuda", 0), capacity_doubles=1 << 20)
+        if os.environ.get("MR_WORKER_NO_EXCHANGE_KNOWN") == "1":      # a host transport that has only `exchange` (the field is optional in rxmd_comm_ops)
+            from rxmd_amd.comm import EXCHANGE_FN
+            tr.ops.exchange_known = EXCHANGE_FN()
         tr.attach(e)
         e.set_atoms_rxff(rec)
         it, est = e.QEq()

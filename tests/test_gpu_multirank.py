@@ -64,6 +64,23 @@ def test_direct_vector_halo_vs_mpi_reference(case, steps, monkeypatch):
     test_vprocs_parity_vs_mpi_reference(case, steps, "1", monkeypatch)
 
 
+@pytest.mark.parametrize("case,steps", [("rdx222_v222_md3", 3), ("example2_v211_md3", 3)])
+def test_one_round_per_stage_between_ranks_vs_mpi_reference(case, steps, monkeypatch):
+    """RXMD_NO_STAGE_PAIRS=1 between REAL ranks: ghost build, migration, vector halos and the force fold walk the six stages one message per
+    round, as the reference does (comm.F90:68-86) -- 8 ranks with corner forwarding, 2 ranks with migration.  Same goldens of the real MPI
+    reference and the same gates as the paired walk."""
+    monkeypatch.setenv("RXMD_NO_STAGE_PAIRS", "1")
+    test_vprocs_parity_vs_mpi_reference(case, steps, "1", monkeypatch)
+
+
+def test_transport_without_exchange_known_vs_mpi_reference(monkeypatch):
+    """A host whose rxmd_comm_ops has a null exchange_known (mr_worker hands the struct over that way): ghost build and migration keep their paired
+    rounds (two `exchange` calls per round), vector halos and the force fold fall back to one `exchange` call per stage with the buffer capacity.
+    2 ranks with migration, same golden and gates."""
+    monkeypatch.setenv("MR_WORKER_NO_EXCHANGE_KNOWN", "1")
+    test_vprocs_parity_vs_mpi_reference("example2_v211_md3", 3, "1", monkeypatch)
+
+
 @pytest.mark.parametrize("case,steps,qeq_mode", [("rdx222_v211_tight", 0, 0), ("example2_v211_md3", 3, 1)])
 def test_native_rccl_with_real_peers_vs_mpi_reference(case, steps, qeq_mode):
     """The native transport with REAL peers: one process per GPU, ncclSend/ncclRecv/ncclAllReduce between two MI355X (runs only on a

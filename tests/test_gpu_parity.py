@@ -347,7 +347,7 @@ def test_migration_across_periodic_boundary_keeps_reference_order():
 
 @pytest.mark.parametrize("case,mc", [("rdx168", (1, 1, 1)), ("rdx168", (5, 5, 5)), ("ice644", (6, 4, 4)), ("sicnp", (1, 1, 1))])
 def test_fused_self_exchange_gives_the_staged_order_bit_for_bit(case, mc, monkeypatch):
-    """Single rank, round 5: the ghost build and the migration as 26 image segments (three / four kernels, one host wait; engine.hip) against the
+    """Single rank, round 5: the ghost build and the migration as 26 image segments (three / four kernels, one host wait; exchange.hip) against the
     six-stage flag -> scan -> append form they replace (RXMD_NO_STAGE_PAIRS=1 keeps it reachable), which is the reference's own procedure
     (comm.F90:55-100,238-257).  Hot atoms so that some cross the faces in every step; compared after 4 steps: the WHOLE local arrays, residents and
     ghosts in local order -- gid, type exactly; positions, charges, velocities, forces bit for bit on ice, to 1e-11 where hydrogen-bond atomics run.  13 A boxes (every atom has up to 26 images, both faces of an axis at once) and a 65 A box (interior atoms)."""
@@ -381,6 +381,59 @@ def test_fused_self_exchange_gives_the_staged_order_bit_for_bit(case, mc, monkey
             assert np.array_equal(f[k], s[k]), k
         else:
             assert np.abs(f[k] - s[k]).max() <= 1e-11 * max(np.abs(s[k]).max(), 1.0), k
+
+
+_PLAIN_ORDER = {}      # case -> (gid, type) of the whole local arrays of a plain single-rank run (the 26-segment form), computed once
+
+
+def _hot_run(case, mc, rccl=False, **kw):
+    """the recipe of the test above: hot velocities (seed 11), QEq, FORCE, 4 steps; the whole local arrays and what atoms() returns"""
+    e = _engine(case, mc, **kw)
+    if rccl:
+        e.init_rccl(e.rccl_unique_id(), 0, 1)
+    n = e.stats()["natoms"]
+    e.set_velocities(np.random.default_rng(11).normal(0, 0.08, (n, 3)))
+    e.QEq(); e.FORCE(); e.step(4)
+    a = e.atoms()
+    r = dict(gid_all=e.debug(4).copy(), type_all=e.debug(5).copy(), pos_all=e.debug(3, width=3).copy(), q_all=e.debug(9).copy(),
+             gid=a["gid"].copy(), pos=a["pos"].copy(), q=a["q"].copy(), f=a["f"].copy(), v=a["v"].copy(), nghost=e.stats()["nghost_force"])
+    e.close()
+    return r
+
+
+@pytest.mark.parametrize("remote", [False, True])
+@pytest.mark.parametrize("case,mc", [("rdx168", (1, 1, 1)), ("ice644", (6, 4, 4)), ("sicnp", (1, 1, 1))])
+def test_six_exchange_rounds_equal_three_bit_for_bit_on_every_transport(case, mc, remote, monkeypatch):
+    """The multi-rank code path on ONE rank (RXMD_FORCE_STAGED=1): pack -> exchange -> unpack for the ghost build, the migration, the vector halos and
+    the force fold, once with a round per axis (+ and - stage together: three rounds per walk) and once with a round per stage (RXMD_NO_STAGE_PAIRS=1:
+    six, what a callback transport without exchange_known and the reference itself do).  remote False: every message a device copy to the rank itself;
+    True: every message through RCCL send/recv to itself (RXMD_FORCE_REMOTE=1).  Same recipe, arrays and tolerances as the test above; the 13 A RDX box
+    gives every atom images through both faces of every axis (where pairing + and - could go wrong), SiC + PQEq 14-double migration records and the
+    shell halo.  The paired run's local order is also the plain single-rank engine's (the 26-segment form; DESIGN 6: the three agree)."""
+    kw = dict(QEq_tol=1e-12, NMAXQEq=2000)
+    if case == "sicnp":
+        kw["pqeq"] = oa.PQEQ_SICNP
+    monkeypatch.delenv("RXMD_NO_STAGE_PAIRS", raising=False)
+    if case not in _PLAIN_ORDER:
+        monkeypatch.delenv("RXMD_FORCE_STAGED", raising=False); monkeypatch.delenv("RXMD_FORCE_REMOTE", raising=False)
+        r = _hot_run(case, mc, **kw)
+        _PLAIN_ORDER[case] = (r["gid_all"], r["type_all"])
+    monkeypatch.setenv("RXMD_FORCE_STAGED", "1")
+    if remote:
+        monkeypatch.setenv("RXMD_FORCE_REMOTE", "1")
+    p = _hot_run(case, mc, rccl=remote, **kw)               # three rounds
+    monkeypatch.setenv("RXMD_NO_STAGE_PAIRS", "1")
+    s = _hot_run(case, mc, rccl=remote, **kw)               # six rounds
+    assert not (p["gid"] == np.arange(1, len(p["gid"]) + 1)).all(), "test needs at least one migration"
+    assert p["nghost"] == s["nghost"] > 0
+    for k in ("gid_all", "type_all", "gid"):
+        assert np.array_equal(p[k], s[k]), k
+    for k in ("pos_all", "q_all", "pos", "q", "v", "f"):
+        if case == "ice644":
+            assert np.array_equal(p[k], s[k]), k
+        else:
+            assert np.abs(p[k] - s[k]).max() <= 1e-11 * max(np.abs(s[k]).max(), 1.0), k
+    assert np.array_equal(p["gid_all"], _PLAIN_ORDER[case][0]) and np.array_equal(p["type_all"], _PLAIN_ORDER[case][1])
 
 
 def test_reference_shaped_entry_points():
