@@ -181,6 +181,24 @@ int rxmd_hip_FORCE_pqeq(rxmd_handle h, int nbuffer, int natoms, const double *at
 int rxmd_hip_put_lex(rxmd_handle h, int natoms, const double *qsfp, const double *qsfv);
 int rxmd_hip_get_lex(rxmd_handle h, int natoms, double *qsfp, double *qsfv);
 
+/* ---- the same path on arrays that already live on the device -------------------------------- */
+/* QEq + FORCE on caller-ordered DEVICE arrays (single rank).  type[natoms] (1..nso), pos3[natoms][3] row-major REAL coordinates, anywhere in
+ * space; gid[natoms] or NULL (= i + 1); q_in[natoms] or NULL; outputs f3[natoms][3], q_out[natoms] (either may be NULL); pe[14], virial6[6] on
+ * the HOST.  `stream`: the hipStream_t the caller produced the inputs on and will consume the outputs on (NULL = the null stream).
+ * The positions are wrapped into the box on the device, r' = r - (n1 a1 + n2 a2 + n3 a3) with n = floor(H^-1 r), triclinic cells included: an atom
+ * already inside keeps its coordinates bit for bit; the caller's arrays are never written.  Charges: q_in are the starting charges of the CG (with
+ * isQEq = 0 the charges used); q_in = NULL starts from the previous call's solution when natoms is unchanged, from zeros otherwise.  Velocities, the
+ * extended-Lagrangian state and forces are zeroed as by rxmd_hip_QEq / rxmd_hip_FORCE.  virial6 = (xx,yy,zz,yz,zx,xy), the sum over residents and
+ * ghosts of r_a f_b THIS call added to the accumulators of rxmd_hip_get_energy (same unit; the accumulators themselves are left as rxmd_hip_force
+ * leaves them).  The engine works on its own stream: it waits for an event recorded on `stream` at entry and makes `stream` wait for one recorded
+ * behind the output kernel; the call itself returns when pe is on the host, as every entry point does.  The first call sizes the engine as
+ * rxmd_hip_set_atoms_rxff does (types and positions are staged through the host once); later calls never leave the device.  natoms may change
+ * between calls within that capacity (RXMD_E_NBUFFER above it).  A type outside the ffield: RXMD_E_ARG, as from the array-shaped entry points.
+ * RXMD_E_ARG also for vprocs other than 1 1 1, an engine created with pqeq_path, isQEq = 2, natoms < 1, NULL type or pos3.
+ * No counterpart in the reference. */
+int rxmd_hip_evaluate_device(rxmd_handle h, int natoms, const long long *gid, const int *type, const double *pos3, const double *q_in,
+                             double *f3, double *q_out, double pe[14], double virial6[6], void *stream);
+
 /* ---- introspection for tests, roofline accounting and the timers table (main.F90:135-182) ---- */
 typedef struct rxmd_stats {
   int natoms, nghost_qeq, nghost_force; /* copyptr(6)-NATOMS after the QEq / FORCE ghost builds */

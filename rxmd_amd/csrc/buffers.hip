@@ -62,7 +62,8 @@ void *pinned_alloc(size_t bytes, bool coherent_mapped) {
 void pinned_free(void *p) { if (p) (void)hipHostFree(p); }
 
 // ---- the table ------------------------------------------------------------------------------------------------------------------------
-constexpr size_t H_SCAL_DOUBLES = 320;   // pinned mirror of the scalars: [0,64) as the device block; [64,192) the two slots of the run-ahead CG loop (qeq.hip); [192,288) the per-type sums of a host transport
+constexpr size_t H_SCAL_DOUBLES = 320;   // pinned mirror of the scalars: [0,64) as the device block; [64,192) the two slots of the run-ahead CG loop (qeq.hip); [192,288) the per-type sums of a host transport; [288,310) the barostat's; [310,316) H_SCAL_EVAL_VIRIAL
+static_assert(H_SCAL_EVAL_VIRIAL + 6 <= H_SCAL_DOUBLES, "the virial of the device-array evaluate call lies inside the pinned mirror");
 constexpr size_t H_ERR_INTS = 32;        // 16 ints of the device error words + 16 (h_cnt) for the counts the host waits for
 constexpr size_t H_SEG_INTS = 32;        // totals of the 26-segment ghost build
 constexpr size_t H_PUB_WORDS = 32;       // words published through pinned memory (sequence number << 32 | value, pinned_wait)

@@ -212,6 +212,7 @@ int rxmd_hip_force(rxmd_handle h, double pe[14]) {
 int rxmd_hip_step(rxmd_handle h, int nsteps) {
   return guarded(h, [&](Engine &e) {
     const auto t0 = std::chrono::steady_clock::now();
+    e.eval_natoms = -1;                              // (migration re-orders the residents: no warm start for a later rxmd_hip_evaluate_device)
     e.step(nsteps);
     e.st.ms_step_total += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   });
@@ -219,7 +220,7 @@ int rxmd_hip_step(rxmd_handle h, int nsteps) {
 
 int rxmd_hip_minimise(rxmd_handle h, double ftol, int max_loops, double *pe, long long *evaluations) {
   int loops = 0;
-  const int rc = guarded(h, [&](Engine &e) { loops = e.minimise(ftol, max_loops > 0 ? max_loops : 500, pe, evaluations); });
+  const int rc = guarded(h, [&](Engine &e) { e.eval_natoms = -1; loops = e.minimise(ftol, max_loops > 0 ? max_loops : 500, pe, evaluations); });
   return rc ? rc : loops;
 }
 
@@ -404,6 +405,12 @@ int rxmd_hip_FORCE_pqeq(rxmd_handle h, int nbuffer, int natoms, const double *at
       RX_HIP(hipMemcpy(f + a * static_cast<size_t>(nbuffer), e.frc[a], sizeof(double) * natoms, hipMemcpyDeviceToHost));
     if (pe) std::memcpy(pe, e.pe, sizeof(double) * 14);
   });
+}
+
+// ---- the same path on arrays that already live on the device (device_io.hip) ----
+int rxmd_hip_evaluate_device(rxmd_handle h, int natoms, const long long *gid, const int *type, const double *pos3, const double *q_in,
+                             double *f3, double *q_out, double pe[14], double virial6[6], void *stream) {
+  return guarded(h, [&](Engine &e) { e.evaluate_device(natoms, gid, type, pos3, q_in, f3, q_out, pe, virial6, static_cast<hipStream_t>(stream)); });
 }
 
 // ---- introspection ----

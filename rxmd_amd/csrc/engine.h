@@ -108,8 +108,10 @@ constexpr int WAVE = 64;
 
 // the device scalar block `scal` (double): [0, S_COUNT) CG scalars (spmv_kernels.h), [32, 48) energies, [48, 54) the stress accumulators astr,
 // [56, 62) PRINTE's sums, [64, 72) staging of the host all-reduce, [128, 192) the two CG snapshot slots (S_SNAP), and the barostat's own
-// 6-vectors behind them: the step-head copy of astr and the step's sums
+// 6-vectors behind them: the step-head copy of astr and the step's sums.  [72, 78): astr as the device-array evaluate call found it (device_io.hip)
 constexpr int SCAL_BAR_HEAD = 192, SCAL_BAR_STEP = 200, SCAL_N = 208;
+constexpr int SCAL_EVAL_HEAD = 72;
+constexpr int H_SCAL_EVAL_VIRIAL = 310;   // pinned mirror h_scal: the six virial sums of the device-array evaluate call (the egress kernel stores them there)
 
 // XCD-aware workgroup order: the dispatcher deals consecutive workgroup ids round-robin to the 8 XCDs (each with its own L2),
 // so without a remap every L2 sees rows from all over the box and re-fetches the whole gather vector.  With it the
@@ -333,6 +335,14 @@ struct Engine {
   // the packed type is split on the device.  Only once the engine is sized (after a first set_atoms_rxff); velocities are zeroed.
   void set_atoms_arrays(int natoms, const double *atype, const double *x, const double *y, const double *z, const double *q, const double *lexp, const double *lexv);
   int get_atoms_rxff(double *rec10, int capacity);
+  // rxmd_hip_evaluate_device (device_io.hip): caller-ordered DEVICE arrays in (wrapped into the box on the way), QEq + FORCE, forces / charges back out;
+  // `user` is the caller's stream, joined to the engine's by an event on either side.  eval_natoms: atoms of the last such call whose charges are
+  // still in q in the caller's order (-1: none -- another entry point has set or moved the atoms since)
+  void evaluate_device(int natoms, const long long *gid_d, const int *type_d, const double *pos3_d, const double *q_in_d, double *f3_d, double *q_out_d,
+                       double pe_out[14], double virial_out[6], hipStream_t user);
+  void size_from_device_arrays(int natoms, const int *type_d, const double *pos3_d, hipStream_t user);
+  hipEvent_t ev_io_in = nullptr, ev_io_out = nullptr;
+  int eval_natoms = -1;
   void build_ghosts_and_lists(bool qeq_prepass = false);   // COPYATOMS(MODE_COPY) + LINKEDLIST + NEIGHBORLIST + 10 A list/hessian, once per step
   void qeq_start_vectors();        // qs, qt, hs, ht of qeq.F90:36-63 and their cell-sorted copy (before the list sweep that uses them)
   int *rows_int = nullptr, *rows_bnd = nullptr; int n_bnd = 0; bool rows_split_pending = false;   // interior / boundary rows (multi-rank)

@@ -131,6 +131,8 @@ Engine::~Engine() {
   if (ev_main) (void)hipEventDestroy(ev_main);
   if (ev_comm) (void)hipEventDestroy(ev_comm);
   if (ev_est) (void)hipEventDestroy(ev_est);
+  if (ev_io_in) (void)hipEventDestroy(ev_io_in);
+  if (ev_io_out) (void)hipEventDestroy(ev_io_out);
   for (auto &pr : ev_pass) for (auto &e2 : pr) if (e2) (void)hipEventDestroy(e2);
   if (comm_stream && comm_stream != stream) (void)hipStreamDestroy(comm_stream);
   if (stream) (void)hipStreamDestroy(stream);
@@ -450,7 +452,7 @@ void Engine::set_atoms_rxff(int natoms, const double *rec) {
   RX_HIP(hipMemcpy(type, ht.data(), sizeof(int) * natoms, hipMemcpyHostToDevice));
   RX_HIP(hipMemcpy(gid, hg.data(), sizeof(long long) * natoms, hipMemcpyHostToDevice));
   atoms_set = true; lists_valid = false; ghosts_valid = false;
-  st.natoms = N;
+  st.natoms = N; eval_natoms = -1;
 }
 
 // atype = type + l2g * 1e-13 (main.F90:582-593) -> type, global id; a type outside the ffield raises the device error word
@@ -484,7 +486,7 @@ void Engine::set_atoms_arrays(int natoms, const double *atype, const double *x, 
   N = natoms; G = natoms;
   atoms_set = true; lists_valid = false; ghosts_valid = false;
   atype_resid = 0.0;
-  st.natoms = N;
+  st.natoms = N; eval_natoms = -1;
   check_device_error("set_atoms_arrays");          // (synchronises: the caller's arrays are free again)
 }
 

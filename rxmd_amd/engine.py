@@ -240,6 +240,16 @@ class RxmdEngine:
         self._chk(self.L.rxmd_hip_FORCE(self.h, nbuf, natoms, _ptr(atype), posf.ctypes.data_as(C.c_void_p), f.ctypes.data_as(C.c_void_p), _ptr(q), _ptr(pe)))
         return f, pe
 
+    # ---- the same path on arrays that already live on the device ----
+    def evaluate_device(self, natoms, type_ptr, pos_ptr, f_ptr, q_out_ptr, gid_ptr=0, q_in_ptr=0, stream=0):
+        """QEq + FORCE on caller-ordered device arrays given as integer addresses (include/rxmd_hip.h: rxmd_hip_evaluate_device): int32 type[natoms],
+        float64 pos[natoms][3] anywhere in space, outputs float64 f[natoms][3] and q_out[natoms] (0: not wanted), optional int64 gid[natoms] and
+        start charges q_in[natoms]; stream: the hipStream_t handle the arrays are produced and consumed on -> (PE(0:13), virial[6]) on the host"""
+        pe = np.zeros(14); vir = np.zeros(6)
+        p = [C.c_void_p(int(a) or None) for a in (gid_ptr, type_ptr, pos_ptr, q_in_ptr, f_ptr, q_out_ptr)]
+        self._chk(self.L.rxmd_hip_evaluate_device(self.h, int(natoms), p[0], p[1], p[2], p[3], p[4], p[5], _ptr(pe), _ptr(vir), C.c_void_p(int(stream) or None)))
+        return pe, vir
+
     # ---- introspection ----
     def stats(self):
         s = RxmdStats(); self._chk(self.L.rxmd_hip_get_stats(self.h, C.byref(s))); return s.asdict()
