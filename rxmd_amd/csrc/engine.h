@@ -198,6 +198,7 @@ struct Buffers {
 constexpr size_t EHB_DON_EXTRA = 64 * 256 + 256;   // donor list beyond one entry per row: 64 sub-lists (bonded.hip EHB_REGIONS) padded to 256
 
 struct ScaleArgs;
+struct WinPassArgs; struct RowPassArgs;   // the operands of the two matrix-pass kernels (spmv_kernels.h)
 struct Engine {
   const Options opt = Options::from_env();   // the environment switches of this engine (options.def), read once at create
   rxmd_config cfg{};
@@ -349,6 +350,22 @@ struct Engine {
   bool rows_split_pending_invalid() const { return n_bnd < 0 || n_bnd > N; }
   bool sums_from_list = false;     // the list sweep left H.(qs,qt) of the CG start vector in sall / sgh
   void qeq();
+  // ---- the pieces of qeq() (qeq.hip) ----
+  // the instance of k_spmv_win<MODE, STORE, PQ, nstep, var, double | float> this engine runs: chosen in ONE place, for the solver and the placement search
+  struct WinInstance { int nstep, var; bool f32; };
+  WinInstance win_instance() const;
+  WinPassArgs win_args(bool roword = false) const;   // the operands of a window pass over the whole grid, no stop flag; roword: the per-row operands by the rows' places (r_*)
+  RowPassArgs row_args() const;                      // the same for the row pass k_spmv
+  // one matrix pass: row sums into ra / rg (store), over all rows or the rows of rowlist (rows_int / rows_bnd: behind the pbase workgroups of the other launch)
+  struct PassCall { int mode; bool store; double2 *ra = nullptr, *rg = nullptr; const int *rowlist = nullptr; int nrows = 0, pbase = 0; const double *stopflag = nullptr; bool roword = false; };
+  int matrix_pass(const PassCall &c);                // returns the number of partial-sum sets (of four) the launch leaves behind partials[pbase * 4]
+  void cg_reduce(int stage, int nsets, const double *stopflag = nullptr);   // the sets -> scal[S_RAW0..3], all ranks, and the scalar algebra of `stage`
+  struct CgCall { int nmax, vb, vb_upd; bool onepass, runahead, est_with_update, cg_scatter; };   // what one QEq call fixes for its loops: iteration cap, grids of the vector kernels, the loop form
+  double qeq_start(const CgCall &c);                 // gradient, Est and first direction of the start vector -> Est (0 when the run-ahead loop will read it later)
+  int qeq_runahead(const CgCall &c, double &Est);    // the two CG loops -> iterations done
+  int qeq_host_paced(const CgCall &c, double &Est);
+  struct KtPair;
+  void qeq_finish(int it, double Est, KtPair t_qeq); // shells, iteration statistics, the call's timer, once: the placement search
   // observe_energy = false (Engine::step, every step but the last of a call): nothing reads this FORCE's energies -- ENbond skips its pair and self
   // energies, PE(11:13) stay 0 in the block that the next observed FORCE overwrites.  Forces and the virial (astr accumulates over steps) are untouched.
   void force(bool defer_host_read = false, bool observe_energy = true);   // defer: the energies stay in the pinned buffer until finish_force() (step(): no host wait between FORCE and the next step)

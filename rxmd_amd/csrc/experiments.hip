@@ -75,13 +75,7 @@ void spmv_bisect_ms(Engine &e, double *out4) {
   if (hipMalloc(reinterpret_cast<void **>(&buf32), sizeof(double) * 4 * (static_cast<size_t>(e.N) + 2)) != hipSuccess) return;
   auto run = [&](auto lv) {
     constexpr int L = decltype(lv)::value;
-    for (int r = 0; r < 11; ++r) {
-      if (r == 1) hipEventRecord(e.ev[2], e.stream);
-      k_spmv_bisect<L><<<rb, 1024, 0, e.stream>>>(e.N, e.S10, e.nb10, e.hess, e.n10, e.xs, e.hst, e.gst, e.type, e.partials, e.wall, e.wgh, buf32);
-    }
-    hipEventRecord(e.ev[3], e.stream); hipEventSynchronize(e.ev[3]);
-    float ms = 0; hipEventElapsedTime(&ms, e.ev[2], e.ev[3]);
-    return static_cast<double>(ms) / 10.0;
+    return timed_launches_ms(e, 1, 10, [&] { k_spmv_bisect<L><<<rb, 1024, 0, e.stream>>>(e.N, e.S10, e.nb10, e.hess, e.n10, e.xs, e.hst, e.gst, e.type, e.partials, e.wall, e.wgh, buf32); });
   };
   out4[0] = run(std::integral_constant<int, 0>{}); out4[1] = run(std::integral_constant<int, 1>{});
   out4[2] = run(std::integral_constant<int, 2>{}); out4[3] = run(std::integral_constant<int, 3>{});
@@ -100,46 +94,29 @@ __global__ void k_rows_to_rank_order(int N, int S10, const int *__restrict__ row
 void spmv_isolated_ms(Engine &e, double *out) {
   for (int k = 0; k < 20; ++k) out[k] = -1.0;
   const int reps = std::max(1, static_cast<int>(e.opt.iso_reps));
-  auto timed = [&](auto launch) {
-    for (int r = 0; r < reps + 1; ++r) {
-      if (r == 1) hipEventRecord(e.ev[2], e.stream);
-      launch();
-    }
-    hipEventRecord(e.ev[3], e.stream); hipEventSynchronize(e.ev[3]);
-    float ms = 0; hipEventElapsedTime(&ms, e.ev[2], e.ev[3]);
-    return static_cast<double>(ms) / reps;
-  };
+  auto timed = [&](auto launch) { return timed_launches_ms(e, 1, reps, launch); };
   if (e.ff.pqeq) return;
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  const WinPassArgs w = e.win_args();               // the engine's own operands; at(values, slots): the same over copies of the two streams
+  auto at = [&](const double *h, const unsigned short *sl) { WinPassArgs c = w; c.hess = h; c.sl10 = sl; return c; };
+  RowPassArgs r = e.row_args(); r.swz = 1;
   const int rounds = 3;                             // the three kernels alternate: one state of the box for all of them
   for (int rd = 0; rd < rounds; ++rd) {
-    if (e.win_valid) {
-      const size_t lds = static_cast<size_t>(e.win_maxunits) * WIN_UNIT * sizeof(double2);
-      acc[0] += timed([&] { k_spmv_win<MODE_HSH, true, false><<<e.win_groups, 64 * WIN_ROWS, lds, e.stream>>>(e.N, e.G, e.S10, e.dff, e.sl10, e.hess, e.n10, e.rows_sorted, e.win_k, e.win_cnt, e.xs, e.hst, e.gst, e.qst, e.q, e.type, e.scal, e.partials, e.wall, e.wgh, e.hsc, e.pqrow, nullptr, e.win_groups, 0, nullptr); });
-    }
-    acc[1] += timed([&] { k_spmv<MODE_HSH, true, false, 1><<<nblk(e.N, 16), 1024, 0, e.stream>>>(e.N, e.S10, e.dff, e.nb10, e.hess, e.n10, e.xs, e.hst, e.gst, e.qst, e.q, e.type, e.scal, e.partials, e.wall, e.wgh, e.hsc, e.pqrow, 1, nullptr, e.N, 0, nullptr); });
+    if (e.win_valid) acc[0] += timed([&] { launch_win<MODE_HSH, true, false>(w); });
+    acc[1] += timed([&] { launch_row<MODE_HSH, true, false, 1>(r); });
   }
   out[1] = acc[1] / rounds;
-  if (e.win_valid) {                               // variant: 384 entries in flight
-    const size_t lds = static_cast<size_t>(e.win_maxunits) * WIN_UNIT * sizeof(double2);
-    double a3 = 0.0;
-    for (int rd = 0; rd < rounds; ++rd)
-      a3 += timed([&] { k_spmv_win<MODE_HSH, true, false, 3><<<e.win_groups, 64 * WIN_ROWS, lds, e.stream>>>(e.N, e.G, e.S10, e.dff, e.sl10, e.hess, e.n10, e.rows_sorted, e.win_k, e.win_cnt, e.xs, e.hst, e.gst, e.qst, e.q, e.type, e.scal, e.partials, e.wall, e.wgh, e.hsc, e.pqrow, nullptr, e.win_groups, 0, nullptr); });
-    out[2] = a3 / rounds;
-    double a4 = 0.0;                                // variant: second batch requested before the barrier (VAR & 2)
-    for (int rd = 0; rd < rounds; ++rd)
-      a4 += timed([&] { k_spmv_win<MODE_HSH, true, false, 2, 2><<<e.win_groups, 64 * WIN_ROWS, lds, e.stream>>>(e.N, e.G, e.S10, e.dff, e.sl10, e.hess, e.n10, e.rows_sorted, e.win_k, e.win_cnt, e.xs, e.hst, e.gst, e.qst, e.q, e.type, e.scal, e.partials, e.wall, e.wgh, e.hsc, e.pqrow, nullptr, e.win_groups, 0, nullptr); });
-    out[3] = a4 / rounds;
-    double a5 = 0.0;                                // the default once more, after the variants (drift of the box)
-    for (int rd = 0; rd < rounds; ++rd)
-      a5 += timed([&] { k_spmv_win<MODE_HSH, true, false><<<e.win_groups, 64 * WIN_ROWS, lds, e.stream>>>(e.N, e.G, e.S10, e.dff, e.sl10, e.hess, e.n10, e.rows_sorted, e.win_k, e.win_cnt, e.xs, e.hst, e.gst, e.qst, e.q, e.type, e.scal, e.partials, e.wall, e.wgh, e.hsc, e.pqrow, nullptr, e.win_groups, 0, nullptr); });
-    out[4] = a5 / rounds;
+  if (e.win_valid) {
+    auto mean = [&](auto launch) { double a = 0.0; for (int rd = 0; rd < rounds; ++rd) a += timed(launch); return a / rounds; };
+    out[2] = mean([&] { launch_win<MODE_HSH, true, false, 3>(w); });          // variant: 384 entries in flight
+    out[3] = mean([&] { launch_win<MODE_HSH, true, false, 2, 2>(w); });       // variant: second batch requested before the barrier (VAR & 2)
+    out[4] = mean([&] { launch_win<MODE_HSH, true, false>(w); });             // the default once more, after the variants (drift of the box)
     {   // interior groups without the ghost-column sums (VAR & 4), with and without the prefetch; default after them once more
       double b0 = 0.0, b1 = 0.0, b2 = 0.0;
       for (int rd = 0; rd < rounds; ++rd) {
-        b0 += timed([&] { k_spmv_win<MODE_HSH, true, false, 2, 6><<<e.win_groups, 64 * WIN_ROWS, lds, e.stream>>>(e.N, e.G, e.S10, e.dff, e.sl10, e.hess, e.n10, e.rows_sorted, e.win_k, e.win_cnt, e.xs, e.hst, e.gst, e.qst, e.q, e.type, e.scal, e.partials, e.wall, e.wgh, e.hsc, e.pqrow, nullptr, e.win_groups, 0, nullptr, e.win_flag); });
-        b1 += timed([&] { k_spmv_win<MODE_HSH, true, false, 2, 2><<<e.win_groups, 64 * WIN_ROWS, lds, e.stream>>>(e.N, e.G, e.S10, e.dff, e.sl10, e.hess, e.n10, e.rows_sorted, e.win_k, e.win_cnt, e.xs, e.hst, e.gst, e.qst, e.q, e.type, e.scal, e.partials, e.wall, e.wgh, e.hsc, e.pqrow, nullptr, e.win_groups, 0, nullptr); });
-        b2 += timed([&] { k_spmv_win<MODE_HSH, true, false, 2, 4><<<e.win_groups, 64 * WIN_ROWS, lds, e.stream>>>(e.N, e.G, e.S10, e.dff, e.sl10, e.hess, e.n10, e.rows_sorted, e.win_k, e.win_cnt, e.xs, e.hst, e.gst, e.qst, e.q, e.type, e.scal, e.partials, e.wall, e.wgh, e.hsc, e.pqrow, nullptr, e.win_groups, 0, nullptr, e.win_flag); });
+        b0 += timed([&] { launch_win<MODE_HSH, true, false, 2, 6>(w); });
+        b1 += timed([&] { launch_win<MODE_HSH, true, false, 2, 2>(w); });
+        b2 += timed([&] { launch_win<MODE_HSH, true, false, 2, 4>(w); });
       }
       out[5] = b0 / rounds; out[6] = b1 / rounds; out[7] = b2 / rounds;
     }
@@ -149,7 +126,6 @@ void spmv_isolated_ms(Engine &e, double *out) {
   // copy with its rows in cell-sorted order, read without the row indirection.
   if (e.win_valid && e.opt.iso_copies) {
     const size_t ne = static_cast<size_t>(e.rows10) * e.S10;
-    const size_t lds = static_cast<size_t>(e.win_maxunits) * WIN_UNIT * sizeof(double2);
     double *h2[4] = {nullptr, nullptr, nullptr, nullptr}; unsigned short *s2[4] = {nullptr, nullptr, nullptr, nullptr};
     bool ok = true;
     for (int c = 0; c < 4 && ok; ++c) {
@@ -165,10 +141,10 @@ void spmv_isolated_ms(Engine &e, double *out) {
     if (ok) {
       for (int round2 = 0; round2 < 2; ++round2)
         for (int c = 0; c < 4; ++c)
-          out[2 + 4 * round2 + c] = timed([&] { k_spmv_win<MODE_HSH, true, false><<<e.win_groups, 64 * WIN_ROWS, lds, e.stream>>>(e.N, e.G, e.S10, e.dff, s2[c], h2[c], e.n10, e.rows_sorted, e.win_k, e.win_cnt, e.xs, e.hst, e.gst, e.qst, e.q, e.type, e.scal, e.partials, e.wall, e.wgh, e.hsc, e.pqrow, nullptr, e.win_groups, 0, nullptr); });
+          out[2 + 4 * round2 + c] = timed([&] { launch_win<MODE_HSH, true, false>(at(h2[c], s2[c])); });
       k_rows_to_rank_order<<<e.N, 256, 0, e.stream>>>(e.N, e.S10, e.rows_sorted, e.hess, e.sl10, h2[3], s2[3]);
-      out[10] = timed([&] { k_spmv_win<MODE_HSH, true, false, 2, 1><<<e.win_groups, 64 * WIN_ROWS, lds, e.stream>>>(e.N, e.G, e.S10, e.dff, s2[3], h2[3], e.n10, e.rows_sorted, e.win_k, e.win_cnt, e.xs, e.hst, e.gst, e.qst, e.q, e.type, e.scal, e.partials, e.wall, e.wgh, e.hsc, e.pqrow, nullptr, e.win_groups, 0, nullptr); });
-      out[11] = timed([&] { k_spmv_win<MODE_HSH, true, false><<<e.win_groups, 64 * WIN_ROWS, lds, e.stream>>>(e.N, e.G, e.S10, e.dff, e.sl10, e.hess, e.n10, e.rows_sorted, e.win_k, e.win_cnt, e.xs, e.hst, e.gst, e.qst, e.q, e.type, e.scal, e.partials, e.wall, e.wgh, e.hsc, e.pqrow, nullptr, e.win_groups, 0, nullptr); });
+      out[10] = timed([&] { launch_win<MODE_HSH, true, false, 2, 1>(at(h2[3], s2[3])); });
+      out[11] = timed([&] { launch_win<MODE_HSH, true, false>(w); });
     } else (void)hipGetLastError();
     for (int c = 0; c < 4; ++c) { if (h2[c]) (void)hipFree(h2[c]); if (s2[c]) (void)hipFree(s2[c]); }
     // ... and on ONE allocation with the value array at different offsets inside it (out[12..19]): a dependence on low address bits would show here
@@ -179,7 +155,7 @@ void spmv_isolated_ms(Engine &e, double *out) {
         for (int c = 0; c < 8; ++c) {
           double *hh = reinterpret_cast<double *>(big + offs[c]);
           hipMemcpyAsync(hh, e.hess, ne * sizeof(double), hipMemcpyDeviceToDevice, e.stream);
-          out[12 + c] = timed([&] { k_spmv_win<MODE_HSH, true, false><<<e.win_groups, 64 * WIN_ROWS, lds, e.stream>>>(e.N, e.G, e.S10, e.dff, e.sl10, hh, e.n10, e.rows_sorted, e.win_k, e.win_cnt, e.xs, e.hst, e.gst, e.qst, e.q, e.type, e.scal, e.partials, e.wall, e.wgh, e.hsc, e.pqrow, nullptr, e.win_groups, 0, nullptr); });
+          out[12 + c] = timed([&] { launch_win<MODE_HSH, true, false>(at(hh, e.sl10)); });
         }
         (void)hipFree(big);
       } else (void)hipGetLastError();
@@ -272,19 +248,11 @@ void spmv_tile_probe_ms(Engine &e, double *out) {
   const size_t lds = sizeof(double2) * 2 * TILE_WS;
   if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_spmv_tile_probe<true>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess) { (void)hipGetLastError(); }
   if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_spmv_tile_probe<false>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess) { (void)hipGetLastError(); }
-  auto timed = [&](auto launch) {
-    for (int r = 0; r < 11; ++r) { if (r == 1) hipEventRecord(e.ev[2], e.stream); launch(); }
-    hipEventRecord(e.ev[3], e.stream); hipEventSynchronize(e.ev[3]);
-    float ms = 0; hipEventElapsedTime(&ms, e.ev[2], e.ev[3]);
-    return static_cast<double>(ms) / 10.0;
-  };
+  auto timed = [&](auto launch) { return timed_launches_ms(e, 1, 10, launch); };
   out[0] = timed([&] { k_spmv_tile_probe<true><<<ntiles, 1024, lds, e.stream>>>(e.N, e.G, e.S10, e.sl10, e.hess, e.n10, e.xs, e.wall, ybuf); });
   out[4] = timed([&] { k_spmv_tile_probe<false><<<ntiles, 1024, lds, e.stream>>>(e.N, e.G, e.S10, e.sl10, e.hess, e.n10, e.xs, e.wall, ybuf); });
   out[1] = timed([&] { k_tile_gather_probe<<<nblk(e.N, 256), 256, 0, e.stream>>>(e.N, ntiles, ybuf, e.wall); });
-  if (e.win_valid) {                                 // the real pass in the same process, after the probes
-    const size_t ldsw = static_cast<size_t>(e.win_maxunits) * WIN_UNIT * sizeof(double2);
-    out[2] = timed([&] { k_spmv_win<MODE_HSH, true, false, 2, WIN_PREFETCH | WIN_LEAN><<<e.win_groups, 64 * WIN_ROWS, ldsw, e.stream>>>(e.N, e.G, e.S10, e.dff, e.sl10, e.hess, e.n10, e.rows_sorted, e.win_k, e.win_cnt, e.xs, e.hst, e.gst, e.qst, e.q, e.type, e.scal, e.partials, e.wall, e.wgh, e.hsc, e.pqrow, nullptr, e.win_groups, 0, nullptr, e.win_flag); });
-  }
+  if (e.win_valid) out[2] = timed([&] { launch_win<MODE_HSH, true, false, 2, WIN_PREFETCH | WIN_LEAN>(e.win_args()); });   // the real pass in the same process, after the probes
   out[3] = (hipGetLastError() == hipSuccess) ? 0.0 : 1.0;
   (void)hipFree(ybuf);
 }

@@ -20,14 +20,11 @@
 #include <cstdio>
 
 #include <cmath>
-#include <cstdlib>
-#include <type_traits>
 #include <memory>
 #include <utility>
 #include <vector>
 
 namespace rxmd {
-
 
 __global__ void __launch_bounds__(256) k_stream_probe(size_t n16, const f64x2 *__restrict__ a, double *__restrict__ out) {
   double s = 0.0;
@@ -39,13 +36,7 @@ __global__ void __launch_bounds__(256) k_stream_probe(size_t n16, const f64x2 *_
 }
 double stream_probe_ms(Engine &e, int blocks) {
   const size_t n16 = static_cast<size_t>(e.rows10) * e.S10 / 2;
-  hipEventRecord(e.ev[2], e.stream);
-  for (int r = 0; r < 5; ++r) k_stream_probe<<<blocks, 256, 0, e.stream>>>(n16, reinterpret_cast<const f64x2 *>(e.hess), e.partials);
-  hipEventRecord(e.ev[3], e.stream);
-  hipEventSynchronize(e.ev[3]);
-  float ms = 0;
-  hipEventElapsedTime(&ms, e.ev[2], e.ev[3]);
-  return ms / 5.0;
+  return timed_launches_ms(e, 0, 5, [&] { k_stream_probe<<<blocks, 256, 0, e.stream>>>(n16, reinterpret_cast<const f64x2 *>(e.hess), e.partials); });
 }
 
 // single-block deterministic reduction of the per-block partials + the scalar algebra between passes
@@ -380,6 +371,81 @@ void Engine::allreduce_scal4(int n) {
   RX_HIP(hipMemcpyAsync(scal + S_RAW0, h_scal + 48, sizeof(double) * n, hipMemcpyHostToDevice, stream));
 }
 
+// ---- the matrix pass: which instance, with which operands ---------------------------------------------------------------------------------------
+// st.spmv_nstep / spmv_var report the instance (bench.py names the instance whose counters it quotes)
+Engine::WinInstance Engine::win_instance() const {
+  // fp32 matrix stream (set_qeq_precision(32), plain QEq): the float instance in the default form, whatever RXMD_SPMV_ONE_TRIP says; a row's first float is
+  // 16-byte aligned because S10 is a multiple of 64 (256 bytes per row stride), checked all the same
+  if (qeq_bits_req == 32 && !ff.pqeq && hess32 != nullptr && (S10 & 3) == 0) return {2, WIN_PREFETCH | WIN_LEAN, true};
+  if (ff.pqeq) return opt.pq_prefetch != 0 ? WinInstance{1, WIN_PREFETCH, false} : WinInstance{2, WIN_PREFETCH | WIN_LEAN, false};
+  const bool one_trip = opt.spmv_one_trip != 0 && max_row10 > 256 && max_row10 <= 384;      // (PQEq: the third stream of 384 entries does not fit the 64 registers of two workgroups per CU)
+  return one_trip ? WinInstance{3, WIN_LEAN, false} : WinInstance{2, WIN_PREFETCH | WIN_LEAN, false};
+}
+WinPassArgs Engine::win_args(bool roword) const {
+  WinPassArgs a{N, G, S10, dff, sl10, hess, hess32, n10, rows_sorted, win_k, win_cnt, xs, hst, gst, qst, q, type, scal, partials, wall, wgh, hsc, pqrow,
+                nullptr, win_groups, 0, nullptr, win_flag, 0, win_maxunits, stream};
+  if (roword) { a.n10 = r_n10; a.type = r_type; a.hst = r_hst; a.gst = r_gst; a.rs_all = r_wall; a.rs_gh = r_wgh; a.roword = 1; }   // per-row operands of the tail by the row's place in rows_sorted (MODE_HSH only)
+  return a;
+}
+RowPassArgs Engine::row_args() const {
+  return RowPassArgs{N, S10, dff, nb10, hess, n10, xs, hst, gst, qst, q, type, scal, partials, wall, wgh, hsc, pqrow, opt.no_xcd_swizzle ? 0 : 1 /* (experiments build only) */,
+                     nullptr, N, 0, nullptr, stream};
+}
+// (mode, store) -> template arguments, once for both kernels
+template <class F> static void with_mode_store(int mode, bool store, F &&f) {
+  using std::integral_constant;
+  if (mode == MODE_HSH) { if (store) f(integral_constant<int, MODE_HSH>{}, std::true_type{}); else f(integral_constant<int, MODE_HSH>{}, std::false_type{}); }
+  else { if (store) f(integral_constant<int, MODE_GRAD>{}, std::true_type{}); else f(integral_constant<int, MODE_GRAD>{}, std::false_type{}); }
+}
+// the 20 instances of k_spmv_win the product can run: {mode} x {store} x plain {<2, 6>, <3, 4>, <2, 6, float>}, PQEq {<1, 2>, <2, 6>}
+static void launch_win_instance(int mode, bool store, bool pq, Engine::WinInstance wi, const WinPassArgs &a) {
+  constexpr int DEF = WIN_PREFETCH | WIN_LEAN;
+  with_mode_store(mode, store, [&](auto m, auto s) {
+    constexpr int M = decltype(m)::value; constexpr bool S = decltype(s)::value;
+    if (!pq && wi.f32 && wi.nstep == 2 && wi.var == DEF) launch_win<M, S, false, 2, DEF, float>(a);
+    else if (!pq && !wi.f32 && wi.nstep == 2 && wi.var == DEF) launch_win<M, S, false, 2, DEF>(a);
+    else if (!pq && !wi.f32 && wi.nstep == 3 && wi.var == WIN_LEAN) launch_win<M, S, false, 3, WIN_LEAN>(a);
+    else if (pq && !wi.f32 && wi.nstep == 1 && wi.var == WIN_PREFETCH) launch_win<M, S, true, 1, WIN_PREFETCH>(a);
+    else if (pq && !wi.f32 && wi.nstep == 2 && wi.var == DEF) launch_win<M, S, true, 2, DEF>(a);
+    else throw EngineError(RXMD_E_STATE, "no window-pass instance <pq " + std::to_string(pq) + ", nstep " + std::to_string(wi.nstep) + ", var " + std::to_string(wi.var) + (wi.f32 ? ", float>" : ", double>"));
+  });
+}
+int Engine::matrix_pass(const PassCall &c) {
+  win_used = false;
+  if (win_valid && opt.spmv_win != 0 && (!c.rowlist || c.rowlist == rows_int || c.rowlist == rows_bnd)) {   // window pass: the group's partners in LDS, 16-bit slots (k_spmv_win)
+    win_used = true;
+    WinPassArgs a = win_args(c.roword);
+    a.grouplist = !c.rowlist ? nullptr : (c.rowlist == rows_int ? win_gint : win_gbnd);    // multi-rank overlap: interior groups while the halo is in flight, then the rest
+    a.ngroups = !c.rowlist ? win_groups : (c.rowlist == rows_int ? win_groups - win_nbnd : win_nbnd);
+    if (a.ngroups == 0) return 0;
+    a.rs_all = c.ra; a.rs_gh = c.rg; a.pbase = c.pbase; a.stopflag = c.stopflag;
+    const WinInstance wi = win_instance();
+    st.spmv_nstep = wi.nstep; st.spmv_var = wi.var; qeq_bits_used = wi.f32 ? 32 : 64;
+    launch_win_instance(c.mode, c.store, ff.pqeq != 0, wi, a);
+    return a.ngroups;
+  }
+  RowPassArgs a = row_args();
+  a.rs_all = c.ra; a.rs_gh = c.rg; a.rowlist = c.rowlist; a.nrows = c.nrows; a.pbase = c.pbase; a.stopflag = c.stopflag;
+  st.spmv_nstep = 0; st.spmv_var = 0;
+  qeq_bits_used = 64;                          // (with 32 requested: the double stream holds the same rounded values)
+  require_nb10();                              // the row form reads the 4-byte entries
+  const bool pq = ff.pqeq != 0, pipe = !opt.spmv_no_pipe;
+  with_mode_store(c.mode, c.store, [&](auto m, auto s) {
+    constexpr int M = decltype(m)::value; constexpr bool S = decltype(s)::value;
+    if (pq) { if (pipe) launch_row<M, S, true, 1>(a); else launch_row<M, S, true, 0>(a); }
+    else { if (pipe) launch_row<M, S, false, 1>(a); else launch_row<M, S, false, 0>(a); }
+  });
+  return a.nblocks();
+}
+void Engine::cg_reduce(int stage, int nsets, const double *stopflag) {
+  double *lvl1 = partials + partials_cap;      // 128 x 4 first-level sums live behind the per-workgroup partials (fixed offset: independent of the cell count of a sparse box)
+  const int fused_stage = multi() ? 0 : stage; // single rank: level-1 sums, final sum and scalar algebra in one launch; several: rank-local sums only (stage 0)
+  k_reduce_fused<<<nsets > 1024 ? 128 : 1, 256, 0, stream>>>(nsets, partials, lvl1, tickets, fused_stage, scal, stopflag);
+  if (!multi()) return;
+  allreduce_scal4();                           // MPI_ALLREDUCE of the rank-local sums
+  k_scalar_algebra<<<1, 64, 0, stream>>>(stage, scal);
+}
+
 // Where the streams of the window pass lie in physical memory is worth up to 15 % of its time (NOTES.md 3: the same pass on copies of the same
 // arrays runs 0.77 ... 0.90 ms, a property of the buffer, repeatable to 0.1-0.5 %, drawn anew by every hipMalloc).  So, once per engine, after the
 // first QEq call that used the window pass: a few more placements of the value / slot (/ shell-core) arrays are tried, each timed with 30 launches
@@ -392,29 +458,18 @@ void Engine::tune_window_placement() {
   const int tries = static_cast<int>(opt.place_tries);       // (round 4: the draws of one box lie between 0.80 and 0.93 ms, a third of them fast: ten draws miss the fast kind in 3 % of the processes, six in 12 %)
   if (tries <= 1 || !win_valid || N < 65536) return;              // (small systems: nothing to gain)
   const size_t ne = static_cast<size_t>(rows10) * S10;
-  {   // a candidate needs a second copy of the streams while it is timed (6.3 GB at 979,776 atoms): not on a device that is nearly full
-    size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < 2 * ne * (ff.pqeq ? 18 : 10)) { (void)hipGetLastError(); return; }
-  }
+  // a candidate needs a second copy of the streams while it is timed (6.3 GB at 979,776 atoms): not on a device that is nearly full
+  auto room_for_candidate = [&] { size_t fr = 0, tot = 0; if (hipMemGetInfo(&fr, &tot) == hipSuccess && fr >= 2 * ne * (ff.pqeq ? 18 : 10)) return true; (void)hipGetLastError(); return false; };
+  if (!room_for_candidate()) return;
   struct Cand {                                                    // freed on every way out, an exception of a copy included
     double *h = nullptr, *c = nullptr; unsigned short *s = nullptr;
     ~Cand() { if (h) (void)hipFree(h); if (s) (void)hipFree(s); if (c) (void)hipFree(c); }
   };
-  const size_t lds = static_cast<size_t>(win_maxunits) * WIN_UNIT * sizeof(double2);
   auto time_pass = [&](const double *h, const unsigned short *sl, const double *hc) {
-    float ms = 0;
-    for (int r = 0; r < 35; ++r) {
-      if (r == 5) hipEventRecord(ev[2], stream);
-      if (ff.pqeq && opt.pq_prefetch != 0) k_spmv_win<MODE_HSH, true, true, 1, WIN_PREFETCH><<<win_groups, 64 * WIN_ROWS, lds, stream>>>(N, G, S10, dff, sl, h, n10, rows_sorted, win_k, win_cnt, xs, hst, gst, qst, q, type, scal, partials, wall, wgh, hc, pqrow, nullptr, win_groups, 0, nullptr);
-      else if (ff.pqeq) k_spmv_win<MODE_HSH, true, true><<<win_groups, 64 * WIN_ROWS, lds, stream>>>(N, G, S10, dff, sl, h, n10, rows_sorted, win_k, win_cnt, xs, hst, gst, qst, q, type, scal, partials, wall, wgh, hc, pqrow, nullptr, win_groups, 0, nullptr);
-      else if (opt.spmv_one_trip != 0 && max_row10 > 256 && max_row10 <= 384 && rows_live) k_spmv_win<MODE_HSH, true, false, 3, WIN_LEAN><<<win_groups, 64 * WIN_ROWS, lds, stream>>>(N, G, S10, dff, sl, h, r_n10, rows_sorted, win_k, win_cnt, xs, r_hst, r_gst, qst, q, r_type, scal, partials, r_wall, r_wgh, hc, pqrow, nullptr, win_groups, 0, nullptr, win_flag, 1);
-      else if (opt.spmv_one_trip != 0 && max_row10 > 256 && max_row10 <= 384) k_spmv_win<MODE_HSH, true, false, 3, WIN_LEAN><<<win_groups, 64 * WIN_ROWS, lds, stream>>>(N, G, S10, dff, sl, h, n10, rows_sorted, win_k, win_cnt, xs, hst, gst, qst, q, type, scal, partials, wall, wgh, hc, pqrow, nullptr, win_groups, 0, nullptr, win_flag);
-      else if (rows_live) k_spmv_win<MODE_HSH, true, false, 2, WIN_PREFETCH | WIN_LEAN><<<win_groups, 64 * WIN_ROWS, lds, stream>>>(N, G, S10, dff, sl, h, r_n10, rows_sorted, win_k, win_cnt, xs, r_hst, r_gst, qst, q, r_type, scal, partials, r_wall, r_wgh, hc, pqrow, nullptr, win_groups, 0, nullptr, win_flag, 1);   // (the form the run-ahead loop launches: per-row operands in row order)
-      else k_spmv_win<MODE_HSH, true, false, 2, WIN_PREFETCH | WIN_LEAN><<<win_groups, 64 * WIN_ROWS, lds, stream>>>(N, G, S10, dff, sl, h, n10, rows_sorted, win_k, win_cnt, xs, hst, gst, qst, q, type, scal, partials, wall, wgh, hc, pqrow, nullptr, win_groups, 0, nullptr, win_flag);
-    }
-    hipEventRecord(ev[3], stream); hipEventSynchronize(ev[3]);
-    hipEventElapsedTime(&ms, ev[2], ev[3]);
-    return static_cast<double>(ms) / 30.0;
+    WinPassArgs a = win_args(rows_live);            // the form the solver runs: its instance, and after a run-ahead loop in row order the per-row operands of that call
+    a.hess = h; a.sl10 = sl; a.hsc = hc;
+    const WinInstance wi = win_instance();
+    return timed_launches_ms(*this, 5, 30, [&] { launch_win_instance(MODE_HSH, true, ff.pqeq != 0, wi, a); });
   };
 #ifdef RXMD_EXPERIMENTS
   // RXMD_PLACE_SCAN=<slabs> (experiments build): is the placement lottery a RULE?  The two streams of the pass are copied into ONE allocation at
@@ -450,12 +505,7 @@ void Engine::tune_window_placement() {
       // memory (hipExtMallocWithFlags(hipDeviceMallocContiguous)) and virtual-memory-management slabs built from physical chunks of a chosen size
       // (hipMemCreate / hipMemMap: 2 MB, 64 MB, 1 GB) -- if the slow draws are allocations the driver had to back with small page fragments, large
       // chunks are always of the fast kind.  Next to each pass time the plain sequential read of the value stream from the same slab.
-      auto seq_ms = [&](const void *ptr) {
-        hipEventRecord(ev[2], stream);
-        for (int r = 0; r < 5; ++r) k_stream_probe<<<num_cu * 8, 256, 0, stream>>>(hb / 16, reinterpret_cast<const f64x2 *>(ptr), partials);
-        hipEventRecord(ev[3], stream); hipEventSynchronize(ev[3]);
-        float ms = 0; hipEventElapsedTime(&ms, ev[2], ev[3]); return static_cast<double>(ms) / 5.0;
-      };
+      auto seq_ms = [&](const void *ptr) { return timed_launches_ms(*this, 0, 5, [&] { k_stream_probe<<<num_cu * 8, 256, 0, stream>>>(hb / 16, reinterpret_cast<const f64x2 *>(ptr), partials); }); };
       auto on_slab = [&](const char *how, char *slab) {
         double *h2 = reinterpret_cast<double *>(slab);
         unsigned short *s2 = reinterpret_cast<unsigned short *>(slab + ((pad + hb + MB2 - 1) / MB2) * MB2);
@@ -546,10 +596,7 @@ void Engine::tune_window_placement() {
   // while a second process on the same box found 0.82 ms).  Each draw costs a copy of the streams while the search runs, bounded by free memory.
   std::vector<std::unique_ptr<Cand>> drawn;
   for (int c = 1; c < tries; ++c) {
-    {
-      size_t fr = 0, tot = 0;
-      if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < 2 * ne * (ff.pqeq ? 18 : 10)) { (void)hipGetLastError(); break; }
-    }
+    if (!room_for_candidate()) break;
     drawn.push_back(std::make_unique<Cand>());
     Cand &cd_ = *drawn.back();
     st.place_draws = c + 1;
@@ -602,195 +649,123 @@ void Engine::qeq() {
   // PQEq: qeq_initialize forms the matrix from the shells as they are now (pqeq.F90:61); a call that follows another without the atoms having moved
   // (no migration in between, so the lists are still valid) must not re-use the rows built from the shells of before the last update
   if (!lists_valid || (ff.pqeq && pq_matrix_stale)) build_ghosts_and_lists(prepass_on);
-  const int nmax = (cfg.isQEq == 1) ? cfg.NMAXQEq : 1;
-  // one wavefront per row, sixteen rows per workgroup: measured faster than a persistent grid-stride launch (1.10 vs 1.28 ms
-  // per pass at 979,776 rows) -- many short waves overlap each other's load / gather / reduce phases (NOTES.md 3, K4/K5)
-  constexpr int SPMV_WPB = 16;                   // wavefronts (= rows) per workgroup of the matrix pass
-  const int rb = nblk(N, SPMV_WPB);
-  const int vb = std::min(nblk(N, 256), 2048);
+  CgCall c{};
+  c.nmax = (cfg.isQEq == 1) ? cfg.NMAXQEq : 1;
+  c.vb = std::min(nblk(N, 256), 2048);
   // the update kernel finishes its own reduction (last workgroup: one set of partials per workgroup, then the scalar algebra): with one
   // workgroup per CU that tail is short -- 45.8 / 39.3 / 33.8 / 32.6 us per launch at 2048 / 1024 / 512 / 256 workgroups, 68 at 4096
-  const int vb_upd = std::min(nblk(N, 256), 256);
-  double *lvl1 = partials + partials_cap;      // 128 x 4 first-level sums live behind the per-workgroup partials (fixed offset: independent of the cell count of a sparse box)
-  const int swz = opt.no_xcd_swizzle ? 0 : 1;       // (experiments build only)
-  const bool pipe = !opt.spmv_no_pipe;
-  const bool win_env = opt.spmv_win != 0;
-  // returns the number of partial-sum sets (of four) the launch leaves behind partials[pbase * 4]
-  const double *stopflag = nullptr;            // run-ahead CG loop only: kernels of an iteration return at once when scal[S_STOP] is set
-  bool pass_roword = false;                    // set by the run-ahead loop while its vectors are in row order
-  auto pass = [&](int mode, bool store, double2 *ra, double2 *rg, const int *rowlist = nullptr, int nrows = 0, int pbase = 0) -> int {
-    win_used = false;
-    if (win_valid && win_env && (!rowlist || rowlist == rows_int || rowlist == rows_bnd)) {   // window pass: the group's partners in LDS, 16-bit slots (k_spmv_win)
-      win_used = true;
-      const int *glist = !rowlist ? nullptr : (rowlist == rows_int ? win_gint : win_gbnd);    // multi-rank overlap: interior groups while the halo is in flight, then the rest
-      const int ng = !rowlist ? win_groups : (rowlist == rows_int ? win_groups - win_nbnd : win_nbnd);
-      if (ng == 0) return 0;
-      const size_t lds = static_cast<size_t>(win_maxunits) * WIN_UNIT * sizeof(double2);
-      const bool one_trip = !ff.pqeq && opt.spmv_one_trip != 0 && max_row10 > 256 && max_row10 <= 384;      // (PQEq: the third stream of 384 entries does not fit the 64 registers of two workgroups per CU)
-      const bool pq_pre = ff.pqeq && opt.pq_prefetch != 0;
-      st.spmv_nstep = pq_pre ? 1 : (one_trip ? 3 : 2); st.spmv_var = pq_pre ? WIN_PREFETCH : (one_trip ? WIN_LEAN : (WIN_PREFETCH | WIN_LEAN));   // what the line below dispatches (bench.py names the instance whose counters it quotes)
-      // fp32 matrix stream (set_qeq_precision(32), plain QEq): the float instance in the default form, whatever RXMD_SPMV_ONE_TRIP says; a row's first float is
-      // 16-byte aligned because S10 is a multiple of 64 (256 bytes per row stride), checked all the same
-      const bool f32 = qeq_bits_req == 32 && !ff.pqeq && hess32 != nullptr && (S10 & 3) == 0;
-      qeq_bits_used = f32 ? 32 : 64;
-      if (f32) { st.spmv_nstep = 2; st.spmv_var = WIN_PREFETCH | WIN_LEAN; }
-      // per-row operands of the tail: by atom, or (run-ahead loop in row order, MODE_HSH only) by the row's place in rows_sorted
-      const int *p_n10 = pass_roword ? r_n10 : n10, *p_type = pass_roword ? r_type : type;
-      const double2 *p_hst = pass_roword ? r_hst : hst; double2 *p_gst = pass_roword ? r_gst : gst;
-#define RX_WIN3(M, S, P) do { if (P && pq_pre) k_spmv_win<M, S, P, 1, WIN_PREFETCH><<<ng, 64 * WIN_ROWS, lds, stream>>>(N, G, S10, dff, sl10, hess, p_n10, rows_sorted, win_k, win_cnt, xs, p_hst, p_gst, qst, q, p_type, scal, partials, ra, rg, hsc, pqrow, glist, ng, pbase, stopflag, win_flag, pass_roword ? 1 : 0); \
-                              else if (one_trip && !P) k_spmv_win<M, S, false, 3, WIN_LEAN><<<ng, 64 * WIN_ROWS, lds, stream>>>(N, G, S10, dff, sl10, hess, p_n10, rows_sorted, win_k, win_cnt, xs, p_hst, p_gst, qst, q, p_type, scal, partials, ra, rg, hsc, pqrow, glist, ng, pbase, stopflag, win_flag, pass_roword ? 1 : 0); \
-                              else k_spmv_win<M, S, P, 2, WIN_PREFETCH | WIN_LEAN><<<ng, 64 * WIN_ROWS, lds, stream>>>(N, G, S10, dff, sl10, hess, p_n10, rows_sorted, win_k, win_cnt, xs, p_hst, p_gst, qst, q, p_type, scal, partials, ra, rg, hsc, pqrow, glist, ng, pbase, stopflag, win_flag, pass_roword ? 1 : 0); } while (0)
-#define RX_WIN32(M, S) k_spmv_win<M, S, false, 2, WIN_PREFETCH | WIN_LEAN, float><<<ng, 64 * WIN_ROWS, lds, stream>>>(N, G, S10, dff, sl10, hess32, p_n10, rows_sorted, win_k, win_cnt, xs, p_hst, p_gst, qst, q, p_type, scal, partials, ra, rg, hsc, pqrow, glist, ng, pbase, stopflag, win_flag, pass_roword ? 1 : 0)
-#define RX_WIN(M, S) do { if (f32) RX_WIN32(M, S); else if (ff.pqeq) RX_WIN3(M, S, true); else RX_WIN3(M, S, false); } while (0)
-      if (mode == MODE_HSH) { if (store) RX_WIN(MODE_HSH, true); else RX_WIN(MODE_HSH, false); }
-      else { if (store) RX_WIN(MODE_GRAD, true); else RX_WIN(MODE_GRAD, false); }
-#undef RX_WIN
-#undef RX_WIN32
-#undef RX_WIN3
-      return ng;
-    }
-    const int rbl = rowlist ? nblk(nrows, SPMV_WPB) : rb;
-    if (rbl == 0) return 0;
-    st.spmv_nstep = 0; st.spmv_var = 0;
-    qeq_bits_used = 64;                          // (with 32 requested: the double stream holds the same rounded values)
-    require_nb10();                              // the row form reads the 4-byte entries
-#define RX_PASS3(M, S, P, PI) k_spmv<M, S, P, PI><<<rbl, 64 * SPMV_WPB, 0, stream>>>(N, S10, dff, nb10, hess, n10, xs, hst, gst, qst, q, type, scal, partials, ra, rg, hsc, pqrow, swz, rowlist, nrows, pbase, stopflag)
-#define RX_PASS(M, S)                                                                                                  \
-  do {                                                                                                                 \
-    if (ff.pqeq) { if (pipe) RX_PASS3(M, S, true, 1); else RX_PASS3(M, S, true, 0); }                                  \
-    else { if (pipe) RX_PASS3(M, S, false, 1); else RX_PASS3(M, S, false, 0); }                                        \
-  } while (0)
-    if (mode == MODE_HSH) { if (store) RX_PASS(MODE_HSH, true); else RX_PASS(MODE_HSH, false); }
-    else { if (store) RX_PASS(MODE_GRAD, true); else RX_PASS(MODE_GRAD, false); }
-#undef RX_PASS
-#undef RX_PASS3
-    return rbl;
-  };
-  auto reduce = [&](int stage, int nb_) {
-    if (!multi()) {                              // single rank: level-1 sums, final sum and scalar algebra in one launch
-      if (nb_ > 1024) k_reduce_fused<<<128, 256, 0, stream>>>(nb_, partials, lvl1, tickets, stage, scal, stopflag);
-      else k_reduce_fused<<<1, 256, 0, stream>>>(nb_, partials, lvl1, tickets, stage, scal, stopflag);
-      return;
-    }
-    if (nb_ > 1024) k_reduce_fused<<<128, 256, 0, stream>>>(nb_, partials, lvl1, tickets, 0, scal);   // stage 0: rank-local sums only
-    else k_reduce_fused<<<1, 256, 0, stream>>>(nb_, partials, lvl1, tickets, 0, scal);
-    allreduce_scal4();                           // MPI_ALLREDUCE of the rank-local sums
-    k_scalar_algebra<<<1, 64, 0, stream>>>(stage, scal);
-  };
+  c.vb_upd = std::min(nblk(N, 256), 256);
+  c.onepass = (cfg.qeq_mode == 1);
+  c.est_with_update = !opt.est_separate; c.cg_scatter = !opt.cg_no_scatter;     // (experiments build only)
+  c.runahead = !multi() && c.onepass && !ff.pqeq && c.est_with_update && !opt.cg_no_runahead;
+  double Est = qeq_start(c);
+  const int it = c.runahead ? qeq_runahead(c, Est) : qeq_host_paced(c, Est);
+  qeq_finish(it, Est, t_qeq);
+}
+
+double Engine::qeq_start(const CgCall &c) {
   RX_HIP(hipMemsetAsync(scal, 0, sizeof(double) * 32, stream));
   h_scal[60] = cfg.QEq_tol;
   RX_HIP(hipMemcpyAsync(scal + S_TOL, h_scal + 60, sizeof(double), hipMemcpyHostToDevice, stream));
-  const bool onepass = (cfg.qeq_mode == 1);
   if (sums_from_list) {
-    k_grad_start<<<vb, 256, 0, stream>>>(N, dff, type, qst, q, sall, sgh, gst, partials, pqrow);
-    reduce(3, vb);
+    k_grad_start<<<c.vb, 256, 0, stream>>>(N, dff, type, qst, q, sall, sgh, gst, partials, pqrow);
+    cg_reduce(3, c.vb);
   } else {
     qeq_start_vectors();
-    const int np0 = pass(MODE_GRAD, onepass, onepass ? sall : nullptr, onepass ? sgh : nullptr);
-    reduce(3, np0);
+    cg_reduce(3, matrix_pass({MODE_GRAD, c.onepass, c.onepass ? sall : nullptr, c.onepass ? sgh : nullptr}));
   }
   k_direction<<<nblk(N, 256), 256, 0, stream>>>(N, 1, scal, gst, hst);
   RX_HIP(hipMemcpyAsync(h_scal, scal, sizeof(double) * S_COUNT, hipMemcpyDeviceToHost, stream));
-  const bool est_with_update_ = !opt.est_separate;  // (experiments build only)
-  // run-ahead loop (below): iteration 0 always happens -- the exit tests of qeq.F90:114-115 compare Est with GEst2 = 1e99 -- so the host does not
+  // run-ahead loop: iteration 0 always happens -- the exit tests of qeq.F90:114-115 compare Est with GEst2 = 1e99 -- so the host does not
   // wait for Est of the start vector; it reads it (for the trace) when the first iteration's Est arrives, which is later in stream order
-  const bool start_async = !multi() && cfg.qeq_mode == 1 && !ff.pqeq && est_with_update_ && !opt.cg_no_runahead && nmax >= 1;
+  const bool start_async = c.runahead && c.nmax >= 1;
   if (!start_async) sync_stream();
-  double GEst2 = 1e99, Est = start_async ? 0.0 : h_scal[S_EST];
+  const double Est = start_async ? 0.0 : h_scal[S_EST];
   est_trace.clear(); est_trace.push_back(Est);      // Est of the start vector, then of every iteration (debug tap 13: the reference's QEQDUMP trace)
-  int it = 0;
-  float ms = 0;
+  return Est;
+}
+
+// ---- run-ahead loop (single rank, qeq_mode 1, plain QEq; RXMD_CG_NO_RUNAHEAD=1 switches it off) ------------------------------------
+// The host is one iteration BEHIND the device: iteration it is queued in full before the host has seen the Est that decides whether it
+// happens.  The decision (qeq.F90:114-115) is made on the device where Est becomes final (scalar_algebra stage 6 -> scal[S_STOP]); the
+// kernels of an iteration that is not to happen return at once; the host reads the same flag.  Iteration counts, charges and every
+// sum are those of the host-paced loop -- what changes is that no host round trip lies between two iterations (on a host that shares its
+// cores with other jobs the blocking loop lost 90 us per iteration: 172 against 80 us of everything that is not the matrix pass).
+int Engine::qeq_runahead(const CgCall &c, double &Est) {
+  if (c.nmax < 1) return 0;                      // (iteration 0 is the host's decision and always happens: GEst2 = 1e99 passes neither exit test)
+  // row order (above: k_rows_enter): the window pass must be the one that runs, and its rows are the places
+  const bool roword = opt.cg_row_order != 0 && win_valid && opt.spmv_win != 0;
+  const int R = win_groups * WIN_ROWS, nmax = c.nmax;
   bool xs_current = false;       // the fused direction kernel leaves the sorted copy of the new (hs,ht) in xs
-  const bool overlap_on = !opt.no_halo_overlap;
-  const bool est_with_update = !opt.est_separate, cg_scatter = !opt.cg_no_scatter;     // (experiments build only)
-  const bool overlap = overlap_on && multi() && onepass && !rows_split_pending_invalid();
-  bool halo_in_flight = false, q_pending = false;
-  // ---- run-ahead loop (single rank, qeq_mode 1, plain QEq; RXMD_CG_NO_RUNAHEAD=1 switches it off) ------------------------------------
-  // The host is one iteration BEHIND the device: iteration it is queued in full before the host has seen the Est that decides whether it
-  // happens.  The decision (qeq.F90:114-115) is made on the device where Est becomes final (scalar_algebra stage 6 -> scal[S_STOP]); the
-  // kernels of an iteration that is not to happen return at once; the host reads the same flag.  Iteration counts, charges and every
-  // sum are those of the loop below -- what changes is that no host round trip lies between two iterations (on a host that shares its
-  // cores with other jobs the blocking loop lost 90 us per iteration: 172 against 80 us of everything that is not the matrix pass).
-  const bool runahead = !multi() && onepass && !ff.pqeq && est_with_update && !opt.cg_no_runahead;
-  if (runahead) {
-    auto exit_test = [&](double prev, double est) {
-      return (0.5 * (std::fabs(prev) + std::fabs(est)) < cfg.QEq_tol) || (std::fabs(prev) > 0.0 && std::fabs(est / prev - 1.0) < cfg.QEq_tol);
-    };
-    // row order (above: k_rows_enter): the window pass must be the one that runs, and its rows are the places
-    const bool roword = opt.cg_row_order != 0 && win_valid && win_env;
-    const int R = win_groups * WIN_ROWS;
-    auto enqueue = [&](int k) {                    // everything of iteration k; on the device a no-op when its stop flag is set
-      stopflag = (k == 0) ? nullptr : scal + S_STOP + (k & 1);    // iteration 0 is decided by the host (Est of the start vector is here already)
-      if (!xs_current) sorted_copy(hst);           // first iteration only: afterwards the direction kernel leaves the sorted copy behind
-      xs_current = false;
-      // the HIP event pair that times the pass rides on every n-th launch only (opt.pass_timing_every, default 8): an event between two dependent
-      // kernels costs the chain ~7 us, two per iteration were 15-20 us of every CG iteration (profiles/r06_ab_pass_events.txt).  Read once the host has
-      // confirmed that the iteration happened (a pass that returned at once is not timed).
-      const bool timed = !opt.no_pass_events && (pass_counter++ % static_cast<unsigned long long>(std::max<long long>(opt.pass_timing_every, 1))) == 0;
-      pass_timed_k[k & 1] = timed;
-      if (timed) hipEventRecord(ev_pass[k & 1][0], stream);
-      pass_roword = roword;
-      const int np1 = pass(MODE_HSH, true, roword ? r_wall : wall, roword ? r_wgh : wgh);
-      pass_roword = false;
-      if (timed) hipEventRecord(ev_pass[k & 1][1], stream);
-      // (round 6, measured and dropped: the pass finishing its own reduction -- chunks of 256 workgroups, the last to arrive adds its chunk, the last chunk
-      //  adds the chunk sums and runs the stage-1 algebra.  The launch of k_reduce_fused goes away, 81 -> 71-74 us per iteration outside the pass, but
-      //  every workgroup's last wavefront then waits for its four stores and a ticket before it frees the workgroup's LDS: the pass in the loop went from
-      //  0.877-0.880 to 0.919-0.924 ms, +36 us per iteration net; profiles/r06_ab_reduce_in_pass.txt)
-      reduce(1, np1);
-      // Est and the stop flags of this iteration reach the host as a snapshot the update kernel's tail stores into pinned host memory (slot k & 1), its
-      // sequence number last: nothing sits between the update and the direction kernel, and the host polls a word of its own memory
-      snap_expect[k & 1] = static_cast<double>(++snap_seq);
-      if (roword) k_cg_update<true><<<vb_upd, 256, 0, stream>>>(R, dff, scal, r_type, r_hst, r_qst, r_wall, r_wgh, r_sall, r_sgh, r_gst, partials, tickets + 1, pqrow, 6 | (((k + 1) & 1) << 4), stopflag,
-                                                                h_scal + 64, snap_expect[k & 1], rows_sorted, N);
-      else k_cg_update<true><<<vb_upd, 256, 0, stream>>>(N, dff, scal, type, hst, qst, wall, wgh, sall, sgh, gst, partials, tickets + 1, pqrow, 6 | (((k + 1) & 1) << 4), stopflag,
-                                                         h_scal + 64, snap_expect[k & 1]);
-      const bool scatter = cg_scatter && k + 1 <= nmax - 1;
-      if (roword) { k_cg_direction<false><<<vb, 256, 0, stream>>>(R, dff, scal, r_type, r_gst, r_hst, r_hst2, r_qst, r_sall, r_sgh, q, partials, tickets + 2, pqrow, -1, G, invpos, g_rrow, scatter ? xs : nullptr, stopflag,
-                                                                  rows_sorted, N, r_xpos); std::swap(r_hst, r_hst2); }
-      else { k_cg_direction<false><<<vb, 256, 0, stream>>>(N, dff, scal, type, gst, hst, hst2, qst, sall, sgh, q, partials, tickets + 2, pqrow, -1, G, invpos, groot, scatter ? xs : nullptr, stopflag); std::swap(hst, hst2); }
-      if (k + 1 <= nmax - 1) { if (!scatter) { if (roword) throw EngineError(RXMD_E_STATE, "row order needs the scatter form of the direction kernel"); sorted_copy(hst); } xs_current = true; }
-    };
-    it = 0;
-    if (nmax >= 1 && (start_async || !exit_test(GEst2, Est))) {
-      GEst2 = Est;
-      if (roword) {                                // the start vectors (qs,qt), (hs,ht) = (gs,gt), the row sums of the start vector: into row order
-        if (!cg_scatter) throw EngineError(RXMD_E_STATE, "row order needs the scatter form of the direction kernel");
-        sorted_copy(hst); xs_current = true;       // (the first iteration's gather copy, from the atom-ordered start direction)
-        k_rows_enter<<<nblk(R, 256), 256, 0, stream>>>(R, N, rows_sorted, type, n10, invpos, qst, hst, gst, sall, sgh, r_qst, r_hst, r_gst, r_sall, r_sgh, r_type, r_n10, r_xpos, rpos);
-        if (G > N) k_ghost_rows<<<nblk(G - N, 256), 256, 0, stream>>>(N, G, groot, rpos, g_rrow);
-        rows_live = true;
-      }
-      enqueue(0);
-      for (it = 1;; ++it) {
-        const bool queued = it <= nmax - 1;
-        if (queued) enqueue(it);                   // ahead of the decision
-        wait_snapshot((it - 1) & 1, snap_expect[(it - 1) & 1]);     // iteration it - 1 has produced its Est and the decision about iteration it
-        if (it == 1 && start_async) est_trace[0] = h_scal[S_EST];      // (the start vector's Est: copied before anything of iteration 0 ran)
-        collect_timers();
-        const double *hs = h_scal + 64 + 64 * ((it - 1) & 1);
-        Est = hs[S_EST];
-        est_trace.push_back(Est);
-        if (pass_timed_k[(it - 1) & 1]) { float pms = 0; if (hipEventElapsedTime(&pms, ev_pass[(it - 1) & 1][0], ev_pass[(it - 1) & 1][1]) == hipSuccess) { pass_timed_ms += pms; pass_timed_n += 1; } }
-        st.spmv_launches += 1;
-        if (!queued) break;                        // NMAXQEq iterations done
-        if (hs[S_STOP + (it & 1)] != 0.0) { if (roword) std::swap(r_hst, r_hst2); else std::swap(hst, hst2); st.spmv_noop_launches += 1; break; }       // iteration it did not happen: its direction kernel wrote nothing, undo the swap
-        GEst2 = Est;
-      }
-      stopflag = nullptr;
-      if (roword) k_rows_exit<<<nblk(R, 256), 256, 0, stream>>>(R, N, rows_sorted, scal, r_qst, qst, q);      // back to atom order: (qs,qt) and q = qs - mu qt
-      else k_apply_q<<<nblk(N, 256), 256, 0, stream>>>(N, scal, qst, q);     // q = qs - mu qt with the mu of the last iteration that happened (qeq.F90:150)
-    }
-    if (ff.pqeq) pqeq_update_shells();
-    nstep_qeq = it; last_est = Est;
-    st.qeq_iters_last = it; st.qeq_iters_total += it; st.qeq_calls += 1; qeq_iters_smooth = qeq_iters_smooth < 0.0 ? it : 0.75 * qeq_iters_smooth + 0.25 * it;
-    // No host wait here (round 5): the kernels of the iteration that did not happen are still in the queue (they return at once and store no snapshot)
-    // and FORCE queues behind them in stream order.  (Until round 5 a sync here cost ~50 us of idle GPU per step.)
-    outer_end(t_qeq);
-    if (!place_tuned && win_used && it >= 1 && qeq_bits_req != 32) { sync_stream(); collect_timers(); tune_window_placement(); }
-    return;
+  auto enqueue = [&](int k) {                    // everything of iteration k; on the device a no-op when its stop flag is set
+    const double *stopflag = (k == 0) ? nullptr : scal + S_STOP + (k & 1);    // the kernels of an iteration return at once when its flag is set; iteration 0 is decided by the host
+    if (!xs_current) sorted_copy(hst);           // first iteration only: afterwards the direction kernel leaves the sorted copy behind
+    xs_current = false;
+    // the HIP event pair that times the pass rides on every n-th launch only (opt.pass_timing_every, default 8): an event between two dependent
+    // kernels costs the chain ~7 us, two per iteration were 15-20 us of every CG iteration (profiles/r06_ab_pass_events.txt).  Read once the host has
+    // confirmed that the iteration happened (a pass that returned at once is not timed).
+    const bool timed = !opt.no_pass_events && (pass_counter++ % static_cast<unsigned long long>(std::max<long long>(opt.pass_timing_every, 1))) == 0;
+    pass_timed_k[k & 1] = timed;
+    if (timed) hipEventRecord(ev_pass[k & 1][0], stream);
+    const int np1 = matrix_pass({MODE_HSH, true, roword ? r_wall : wall, roword ? r_wgh : wgh, nullptr, 0, 0, stopflag, roword});
+    if (timed) hipEventRecord(ev_pass[k & 1][1], stream);
+    // (round 6, measured and dropped: the pass finishing its own reduction -- chunks of 256 workgroups, the last to arrive adds its chunk, the last chunk
+    //  adds the chunk sums and runs the stage-1 algebra.  The launch of k_reduce_fused goes away, 81 -> 71-74 us per iteration outside the pass, but
+    //  every workgroup's last wavefront then waits for its four stores and a ticket before it frees the workgroup's LDS: the pass in the loop went from
+    //  0.877-0.880 to 0.919-0.924 ms, +36 us per iteration net; profiles/r06_ab_reduce_in_pass.txt)
+    cg_reduce(1, np1, stopflag);
+    // Est and the stop flags of this iteration reach the host as a snapshot the update kernel's tail stores into pinned host memory (slot k & 1), its
+    // sequence number last: nothing sits between the update and the direction kernel, and the host polls a word of its own memory
+    snap_expect[k & 1] = static_cast<double>(++snap_seq);
+    if (roword) k_cg_update<true><<<c.vb_upd, 256, 0, stream>>>(R, dff, scal, r_type, r_hst, r_qst, r_wall, r_wgh, r_sall, r_sgh, r_gst, partials, tickets + 1, pqrow, 6 | (((k + 1) & 1) << 4), stopflag,
+                                                                  h_scal + 64, snap_expect[k & 1], rows_sorted, N);
+    else k_cg_update<true><<<c.vb_upd, 256, 0, stream>>>(N, dff, scal, type, hst, qst, wall, wgh, sall, sgh, gst, partials, tickets + 1, pqrow, 6 | (((k + 1) & 1) << 4), stopflag,
+                                                           h_scal + 64, snap_expect[k & 1]);
+    const bool scatter = c.cg_scatter && k + 1 <= nmax - 1;
+    if (roword) { k_cg_direction<false><<<c.vb, 256, 0, stream>>>(R, dff, scal, r_type, r_gst, r_hst, r_hst2, r_qst, r_sall, r_sgh, q, partials, tickets + 2, pqrow, -1, G, invpos, g_rrow, scatter ? xs : nullptr, stopflag,
+                                                                    rows_sorted, N, r_xpos); std::swap(r_hst, r_hst2); }
+    else { k_cg_direction<false><<<c.vb, 256, 0, stream>>>(N, dff, scal, type, gst, hst, hst2, qst, sall, sgh, q, partials, tickets + 2, pqrow, -1, G, invpos, groot, scatter ? xs : nullptr, stopflag); std::swap(hst, hst2); }
+    if (k + 1 <= nmax - 1) { if (!scatter) { if (roword) throw EngineError(RXMD_E_STATE, "row order needs the scatter form of the direction kernel"); sorted_copy(hst); } xs_current = true; }
+  };
+  if (roword) {                                // the start vectors (qs,qt), (hs,ht) = (gs,gt), the row sums of the start vector: into row order
+    if (!c.cg_scatter) throw EngineError(RXMD_E_STATE, "row order needs the scatter form of the direction kernel");
+    sorted_copy(hst); xs_current = true;       // (the first iteration's gather copy, from the atom-ordered start direction)
+    k_rows_enter<<<nblk(R, 256), 256, 0, stream>>>(R, N, rows_sorted, type, n10, invpos, qst, hst, gst, sall, sgh, r_qst, r_hst, r_gst, r_sall, r_sgh, r_type, r_n10, r_xpos, rpos);
+    if (G > N) k_ghost_rows<<<nblk(G - N, 256), 256, 0, stream>>>(N, G, groot, rpos, g_rrow);
+    rows_live = true;
   }
-  for (it = 0; it <= nmax - 1; ++it) {
+  enqueue(0);
+  int it = 1;
+  for (;; ++it) {
+    const bool queued = it <= nmax - 1;
+    if (queued) enqueue(it);                   // ahead of the decision
+    wait_snapshot((it - 1) & 1, snap_expect[(it - 1) & 1]);     // iteration it - 1 has produced its Est and the decision about iteration it
+    if (it == 1) est_trace[0] = h_scal[S_EST];      // (the start vector's Est: copied before anything of iteration 0 ran)
+    collect_timers();
+    const double *hs = h_scal + 64 + 64 * ((it - 1) & 1);
+    Est = hs[S_EST];
+    est_trace.push_back(Est);
+    if (pass_timed_k[(it - 1) & 1]) { float pms = 0; if (hipEventElapsedTime(&pms, ev_pass[(it - 1) & 1][0], ev_pass[(it - 1) & 1][1]) == hipSuccess) { pass_timed_ms += pms; pass_timed_n += 1; } }
+    st.spmv_launches += 1;
+    if (!queued) break;                        // NMAXQEq iterations done
+    if (hs[S_STOP + (it & 1)] != 0.0) { if (roword) std::swap(r_hst, r_hst2); else std::swap(hst, hst2); st.spmv_noop_launches += 1; break; }       // iteration it did not happen: its direction kernel wrote nothing, undo the swap
+  }
+  if (roword) k_rows_exit<<<nblk(R, 256), 256, 0, stream>>>(R, N, rows_sorted, scal, r_qst, qst, q);      // back to atom order: (qs,qt) and q = qs - mu qt
+  else k_apply_q<<<nblk(N, 256), 256, 0, stream>>>(N, scal, qst, q);     // q = qs - mu qt with the mu of the last iteration that happened (qeq.F90:150)
+  return it;
+}
+
+// ---- host-paced loop: the host waits for Est of an iteration before it queues the next (several ranks, PQEq, qeq_mode 0, RXMD_CG_NO_RUNAHEAD=1) ----
+int Engine::qeq_host_paced(const CgCall &c, double &Est) {
+  const int nmax = c.nmax;
+  const bool onepass = c.onepass;
+  double GEst2 = 1e99; float ms = 0;
+  bool xs_current = false;       // the fused direction kernel leaves the sorted copy of the new (hs,ht) in xs
+  const bool overlap = !opt.no_halo_overlap && multi() && onepass && !rows_split_pending_invalid();
+  bool halo_in_flight = false, q_pending = false;
+  auto est_to_host = [&] { RX_HIP(hipMemcpyAsync(h_scal, scal, sizeof(double) * S_COUNT, hipMemcpyDeviceToHost, stream)); RX_HIP(hipEventRecord(ev_est, stream)); };
+  int it = 0;
+  for (; it <= nmax - 1; ++it) {
     if (0.5 * (std::fabs(GEst2) + std::fabs(Est)) < cfg.QEq_tol) break;                          // qeq.F90:114
     if (std::fabs(GEst2) > 0.0 && std::fabs(Est / GEst2 - 1.0) < cfg.QEq_tol) break;            // qeq.F90:115
     GEst2 = Est;
@@ -799,46 +774,42 @@ void Engine::qeq() {
     if (halo_in_flight) {
       // multi-rank overlap: the (hs,ht) halo of this iteration was started on the second stream right after the direction update;
       // rows without a ghost partner do not need it
-      const int n_int = N - n_bnd;
       if (timed_it) hipEventRecord(ev[2], stream);
-      const int np_int = pass(MODE_HSH, onepass, wall, wgh, rows_int, n_int, 0);
+      const int np_int = matrix_pass({MODE_HSH, onepass, wall, wgh, rows_int, N - n_bnd, 0});
       join_comm_stream();
-      const int np_bnd = pass(MODE_HSH, onepass, wall, wgh, rows_bnd, n_bnd, np_int);
+      const int np_bnd = matrix_pass({MODE_HSH, onepass, wall, wgh, rows_bnd, n_bnd, np_int});
       if (timed_it) hipEventRecord(ev[3], stream);
-      reduce(1, np_int + np_bnd);
+      cg_reduce(1, np_int + np_bnd);
       halo_in_flight = false;
     } else {
       if (!xs_current) sorted_copy(hst);                                                         // QCOPY2, qeq.F90:93,164
       xs_current = false;
       if (timed_it) hipEventRecord(ev[2], stream);
-      const int np1 = pass(MODE_HSH, onepass, onepass ? wall : nullptr, onepass ? wgh : nullptr);
+      const int np1 = matrix_pass({MODE_HSH, onepass, onepass ? wall : nullptr, onepass ? wgh : nullptr});
       if (timed_it) hipEventRecord(ev[3], stream);
-      reduce(1, np1);
+      cg_reduce(1, np1);
     }
     if (onepass) {       // qeq_mode 1: one matrix pass per iteration; gradient and Est by recurrence on the stored row sums
       const bool fuse = !multi();                  // single rank: every reduction finishes in-kernel; multi: sums, all-reduce, algebra
       // plain QEq: Est rides on the update kernel's sums (quadratic in mu, scalar_algebra stage 6) -- multi-rank: two all-reduces per
       // iteration instead of three; any rank count: Est is final BEFORE the direction kernel, so its copy to the host, the host's exit
       // test and the launch of the next matrix pass all run underneath the direction update and the sorted copy / halo
-      const bool est3 = !ff.pqeq && est_with_update;
-      if (est3) k_cg_update<true><<<vb_upd, 256, 0, stream>>>(N, dff, scal, type, hst, qst, wall, wgh, sall, sgh, gst, partials, tickets + 1, pqrow, fuse ? 6 : 0, nullptr);
-      else k_cg_update<false><<<vb_upd, 256, 0, stream>>>(N, dff, scal, type, hst, qst, wall, wgh, sall, sgh, gst, partials, tickets + 1, pqrow, fuse ? 4 : 0, nullptr);
+      const bool est3 = !ff.pqeq && c.est_with_update;
+      if (est3) k_cg_update<true><<<c.vb_upd, 256, 0, stream>>>(N, dff, scal, type, hst, qst, wall, wgh, sall, sgh, gst, partials, tickets + 1, pqrow, fuse ? 6 : 0, nullptr);
+      else k_cg_update<false><<<c.vb_upd, 256, 0, stream>>>(N, dff, scal, type, hst, qst, wall, wgh, sall, sgh, gst, partials, tickets + 1, pqrow, fuse ? 4 : 0, nullptr);
       if (!fuse) { allreduce_scal4(est3 ? 8 : 4); k_scalar_algebra<<<1, 64, 0, stream>>>(est3 ? 6 : 4, scal); }
-      if (est3) { RX_HIP(hipMemcpyAsync(h_scal, scal, sizeof(double) * S_COUNT, hipMemcpyDeviceToHost, stream)); RX_HIP(hipEventRecord(ev_est, stream)); }
+      if (est3) est_to_host();
       // the direction update runs over the residents in atom order (every access coalesced); the cell-sorted copy with the images
       // is one gather pass queued behind it (sorted_copy).  Doing both in one kernel over the sorted positions
       // (five random 16-byte accesses per atom) was 0.4 ms per step slower.
       // single rank: the direction kernel also scatters the new (hs,ht) to its cell-sorted positions, residents and their periodic images -- the
       // separate gather pass (k_sorted_vec, 12 us per iteration) is gone (RXMD_CG_NO_SCATTER=1 restores it)
-      const bool scatter = fuse && cg_scatter && it + 1 <= nmax - 1;
-      if (est3) k_cg_direction<false><<<vb, 256, 0, stream>>>(N, dff, scal, type, gst, hst, hst2, qst, sall, sgh, q, partials, tickets + 2, pqrow, -1, G, invpos, groot, scatter ? xs : nullptr, nullptr);
-      else k_cg_direction<true><<<vb_upd, 256, 0, stream>>>(N, dff, scal, type, gst, hst, hst2, qst, sall, sgh, q, partials, tickets + 2, pqrow, fuse ? 5 : 0, G, invpos, groot, scatter ? xs : nullptr, nullptr);
+      const bool scatter = fuse && c.cg_scatter && it + 1 <= nmax - 1;
+      if (est3) k_cg_direction<false><<<c.vb, 256, 0, stream>>>(N, dff, scal, type, gst, hst, hst2, qst, sall, sgh, q, partials, tickets + 2, pqrow, -1, G, invpos, groot, scatter ? xs : nullptr, nullptr);
+      else k_cg_direction<true><<<c.vb_upd, 256, 0, stream>>>(N, dff, scal, type, gst, hst, hst2, qst, sall, sgh, q, partials, tickets + 2, pqrow, fuse ? 5 : 0, G, invpos, groot, scatter ? xs : nullptr, nullptr);
       q_pending = est3;
       if (!fuse && !est3) { allreduce_scal4(); k_scalar_algebra<<<1, 64, 0, stream>>>(5, scal); }
-      if (!est3) {       // PQEq: Est comes out of the direction kernel; the host still waits for this copy only, not for the sorted copy behind it
-        RX_HIP(hipMemcpyAsync(h_scal, scal, sizeof(double) * S_COUNT, hipMemcpyDeviceToHost, stream));
-        RX_HIP(hipEventRecord(ev_est, stream));
-      }
+      if (!est3) est_to_host();       // PQEq: Est comes out of the direction kernel; the host still waits for this copy only, not for the sorted copy behind it
       std::swap(hst, hst2);
       xs_current = false;
       if (!overlap && it + 1 <= nmax - 1) {        // sorted copy (multi-rank: after the (hs,ht) halo) queued before the host waits for Est
@@ -861,14 +832,14 @@ void Engine::qeq() {
       st.spmv_launches += 1;
       continue;
     }
-    k_update_qst<<<vb, 256, 0, stream>>>(N, scal, hst, qst, partials);
-    reduce(2, vb);
+    k_update_qst<<<c.vb, 256, 0, stream>>>(N, scal, hst, qst, partials);
+    cg_reduce(2, c.vb);
     k_apply_q<<<nblk(N, 256), 256, 0, stream>>>(N, scal, qst, q);
     sorted_copy(qst);                                                                            // QCOPY1, qeq.F90:153
     hipEventRecord(ev[4], stream);
-    const int np2 = pass(MODE_GRAD, false, nullptr, nullptr);
+    const int np2 = matrix_pass({MODE_GRAD, false});
     hipEventRecord(ev[5], stream);
-    reduce(3, np2);
+    cg_reduce(3, np2);
     k_direction<<<nblk(N, 256), 256, 0, stream>>>(N, 0, scal, gst, hst);
     RX_HIP(hipMemcpyAsync(h_scal, scal, sizeof(double) * S_COUNT, hipMemcpyDeviceToHost, stream));
     sync_stream();
@@ -881,11 +852,18 @@ void Engine::qeq() {
   }
   if (halo_in_flight) join_comm_stream();             // the loop ended while a halo it will not use was still in flight
   if (q_pending) k_apply_q<<<nblk(N, 256), 256, 0, stream>>>(N, scal, qst, q);     // (the direction kernel without Est leaves q to the end)
+  return it;
+}
+
+void Engine::qeq_finish(int it, double Est, KtPair t_qeq) {
   if (ff.pqeq) pqeq_update_shells();                  // pqeq.F90:169
   nstep_qeq = it; last_est = Est;
   st.qeq_iters_last = it; st.qeq_iters_total += it; st.qeq_calls += 1; qeq_iters_smooth = qeq_iters_smooth < 0.0 ? it : 0.75 * qeq_iters_smooth + 0.25 * it;
+  // No host wait here (round 5): after a run-ahead loop the kernels of the iteration that did not happen are still in the queue (they return at once and store
+  // no snapshot) and FORCE queues behind them in stream order.  (Until round 5 a sync here cost ~50 us of idle GPU per step.)
   outer_end(t_qeq);
   if (!place_tuned && win_used && it >= 1 && qeq_bits_req != 32) { sync_stream(); collect_timers(); tune_window_placement(); }
 }
 
 }  // namespace rxmd
+

@@ -167,7 +167,9 @@ __global__ void __launch_bounds__(1024) k_spmv(int N, int S10, DevFF ff, const i
 // (A timing probe with synthetic slots promised 0.76 against 0.93 ms of k_spmv before anything real was built; the real pass: 0.80 against 0.89 ms
 // back to back in one process, NOTES.md 3.  Variants are compared compiled side by side through VAR and debug tap 104.)
 // FORM (bit set): WIN_PREFETCH = the second batch of a row is requested before the workgroup's barrier; WIN_LEAN = groups without a ghost partner skip the
-// ghost-column sums; WIN_RANKROWS = experiments build only.  Plain QEq runs WIN_PREFETCH | WIN_LEAN (RXMD_SPMV_ONE_TRIP=1 and rows of 257-384 entries: NSTEP 3, WIN_LEAN), PQEq NSTEP 1 with WIN_PREFETCH (RXMD_PQ_PREFETCH=0: NSTEP 2, no prefetch).
+// ghost-column sums; WIN_RANKROWS = experiments build only.  Plain QEq runs WIN_PREFETCH | WIN_LEAN (RXMD_SPMV_ONE_TRIP=1 and rows of 257-384 entries: NSTEP 3, WIN_LEAN), PQEq NSTEP 1 with WIN_PREFETCH
+// (RXMD_PQ_PREFETCH=0: the instance <PQ, 2, WIN_PREFETCH | WIN_LEAN>, in which both bits are inert -- with PQ the prefetch form needs NSTEP 1 and the lean body is plain QEq's -- i.e. two
+// batches of 128 entries in one register set, loaded and then used).  Which instance runs: Engine::win_instance (qeq.hip).
 // VT (value type of the matrix stream): double, or float for the mixed-precision solver (Engine::set_qeq_precision(32), plain QEq, NSTEP 2, WIN_PREFETCH |
 // WIN_LEAN only): the values were rounded once to REAL(4) by the list sweep and arrive as float pairs -- 8 bytes per lane and request, 6 instead of 10
 // bytes per entry with the slot -- sit in the register sets as floats and are widened where they are used; window, slots, products, sums, tail and
@@ -363,6 +365,47 @@ __global__ void __launch_bounds__(64 * WIN_ROWS, 8) k_spmv_win(int N, int G, int
   }
   };
   if (gh) whole(std::true_type{}); else whole(std::false_type{});
+}
+
+// ---- host side: the ONE launch site of each pass kernel --------------------------------------------------------------------------------------
+// The operands of a launch as a plain struct in the kernel's order; launch_win / launch_row expand it into the positional call (the kernels keep their
+// positional signatures: the struct is not a kernel argument).  Engine::win_args / row_args (qeq.hip) fill one for the common case -- atom order, whole
+// grid, no stop flag -- and a caller overrides the fields it differs in.
+struct WinPassArgs {
+  int N, G, S10; DevFF ff; const unsigned short *sl10; const double *hess; const float *hess32; const int *n10, *rows_sorted, *win_k, *win_cnt;   // (hess / hess32: the value stream the instance's VT names)
+  const double2 *xv, *hst; double2 *gst; const double2 *qst; const double *q; const int *type; const double *scal; double *partials; double2 *rs_all, *rs_gh; const double *hsc; const double4 *pqrow;
+  const int *grouplist; int ngroups, pbase; const double *stopflag; const int *gflags; int roword;
+  int win_maxunits; hipStream_t stream;               // geometry: ngroups workgroups of WIN_ROWS wavefronts, the largest window of the build in LDS
+};
+template <int MODE, bool STORE, bool PQ, int NSTEP = 2, int VAR = 0, class VT = double>
+inline void launch_win(const WinPassArgs &a) {
+  const VT *values = [&] { if constexpr (std::is_same<VT, float>::value) return a.hess32; else return a.hess; }();
+  k_spmv_win<MODE, STORE, PQ, NSTEP, VAR, VT><<<a.ngroups, 64 * WIN_ROWS, static_cast<size_t>(a.win_maxunits) * WIN_UNIT * sizeof(double2), a.stream>>>(
+      a.N, a.G, a.S10, a.ff, a.sl10, values, a.n10, a.rows_sorted, a.win_k, a.win_cnt, a.xv, a.hst, a.gst, a.qst, a.q, a.type, a.scal, a.partials, a.rs_all, a.rs_gh, a.hsc, a.pqrow,
+      a.grouplist, a.ngroups, a.pbase, a.stopflag, a.gflags, a.roword);
+}
+// one wavefront per row, sixteen rows per workgroup: measured faster than a persistent grid-stride launch (1.10 vs 1.28 ms
+// per pass at 979,776 rows) -- many short waves overlap each other's load / gather / reduce phases (NOTES.md 3, K4/K5)
+constexpr int SPMV_WPB = 16;                   // wavefronts (= rows) per workgroup of the row pass
+struct RowPassArgs {
+  int N, S10; DevFF ff; const int *nb10; const double *hess; const int *n10;
+  const double2 *xv, *hst; double2 *gst; const double2 *qst; const double *q; const int *type; const double *scal; double *partials;
+  double2 *rs_all, *rs_gh; const double *hsc; const double4 *pqrow; int swz; const int *rowlist; int nrows, pbase; const double *stopflag;
+  hipStream_t stream;
+  int nblocks() const { return nblk(rowlist ? nrows : N, SPMV_WPB); }
+};
+template <int MODE, bool STORE, bool PQ, int PIPE>
+inline void launch_row(const RowPassArgs &a) {
+  k_spmv<MODE, STORE, PQ, PIPE><<<a.nblocks(), 64 * SPMV_WPB, 0, a.stream>>>(a.N, a.S10, a.ff, a.nb10, a.hess, a.n10, a.xv, a.hst, a.gst, a.qst, a.q, a.type, a.scal, a.partials, a.rs_all, a.rs_gh, a.hsc, a.pqrow, a.swz,
+                                                                            a.rowlist, a.nrows, a.pbase, a.stopflag);
+}
+
+// the mean time [ms] of `reps` launches behind `warm` untimed ones (events ev[2], ev[3] of the engine; returns when the last launch is through)
+template <class F> inline double timed_launches_ms(Engine &e, int warm, int reps, F &&launch) {
+  for (int r = 0; r < warm + reps; ++r) { if (r == warm) hipEventRecord(e.ev[2], e.stream); launch(); }
+  hipEventRecord(e.ev[3], e.stream); hipEventSynchronize(e.ev[3]);
+  float ms = 0; hipEventElapsedTime(&ms, e.ev[2], e.ev[3]);
+  return static_cast<double>(ms) / reps;
 }
 
 }  // namespace rxmd

@@ -629,6 +629,45 @@ def test_window_pass_and_row_pass_are_the_same_operator(case, mc, qeq_mode, monk
     assert min(d0, d1) <= 2e-4 * np.abs(to).max(), (d0, d1)       # (measured 5.5e-5 on RDX 2 x 2 x 2, qeq_mode 0)
 
 
+@pytest.mark.parametrize("qeq_mode", [0, 1])
+@pytest.mark.parametrize("case,mc,switch,nstep_on,nstep_off", [("ice644", (6, 4, 4), "RXMD_SPMV_ONE_TRIP=1", 3, 2), ("sicnp", (1, 1, 1), "RXMD_PQ_PREFETCH=0", 2, 1)])
+def test_selectable_window_instances_are_the_same_operator(case, mc, switch, nstep_on, nstep_off, qeq_mode, monkeypatch):
+    """Two instances of the window pass run only behind a switch: RXMD_SPMV_ONE_TRIP=1 takes k_spmv_win<.., 3, WIN_LEAN> when the longest row has
+    257-384 entries (water: 2,304 atoms, rows of 345-358 entries -- every row one trip of 384), RXMD_PQ_PREFETCH=0 takes PQEq's <.., 2, 6> instead of
+    its one-batch prefetch form (the nanoparticle: 547 atoms, rows of 107-303 entries).  Same matrix, same vectors, the products of a row added in another
+    order: the gates of the window / row pass comparison above, and the stats say that the two engines ran different instances."""
+    kw = dict(QEq_tol=1e-12, NMAXQEq=2000)
+    if case == "sicnp":
+        kw["pqeq"] = oa.PQEQ_SICNP
+    o = _oracle(case, mc, **kw)
+    if "pqeq" in kw:
+        o.set_pqeq_clean(1)
+    o.qeq(); o.force()
+    name, value = switch.split("=")
+    res = {}
+    for on in (True, False):
+        if on:
+            monkeypatch.setenv(name, value)          # read at rxmd_hip_create
+        else:
+            monkeypatch.delenv(name, raising=False)
+        e = _engine(case, mc, qeq_mode=qeq_mode, **kw)
+        it, est = e.QEq(); pe = e.FORCE(); a = e.atoms(); st = e.stats()
+        assert st["win_in_use"] == 1, st
+        if case == "ice644":
+            assert 256 < st["max_n10"] <= 384, st["max_n10"]
+        assert st["spmv_nstep"] == (nstep_on if on else nstep_off), (on, st["spmv_nstep"], st["spmv_var"])
+        assert q_err(a["q"], o.charges()) <= QTOL
+        assert f_err(a["f"], o.forces()) <= FTOL
+        assert abs(est - o.trace()[-1, 0]) <= 1e-9 * abs(est)
+        res[on] = (a["q"].copy(), a["f"].copy(), pe, e.debug(13, cap=4096).copy(), it)
+        e.close()
+    assert q_err(res[True][0], res[False][0]) <= 1e-7 and f_err(res[True][1], res[False][1]) <= 5e-7
+    assert e_err(res[True][2], res[False][2]) <= 1e-8
+    ta, tb = res[True][3], res[False][3]
+    assert len(ta) == res[True][4] + 1 and len(tb) == res[False][4] + 1 and min(len(ta), len(tb)) >= 3
+    assert np.abs(ta[:3] - tb[:3]).max() <= 1e-10 * np.abs(tb[:3]).max()          # start vector and first two iterations: rounding of the row sums only
+
+
 @pytest.mark.parametrize("case,mc", [("rdx168", (1, 1, 1)), ("rdx222", (2, 2, 2)), ("rdx168", (6, 6, 6)), ("ice644", (6, 4, 4)), ("sicnp547", (1, 1, 1)), ("pbt2272", (1, 1, 1)), ("mos2_tri324", (3, 3, 2))])
 def test_window_slots_lead_back_to_the_list_entries(case, mc):
     """The window form of the 10 A matrix, structurally: every list entry's 16-bit slot, looked up in the window of its row's group (win_k / win_cnt,
