@@ -138,7 +138,7 @@ void Engine::accumulate_stress(bool kinetic) {
   const int n = kinetic ? N : G, nb = 240;
   if (kinetic) k_stress_partial<<<nb, 256, 0, stream>>>(n, vel[0], vel[1], vel[2], vel[0], vel[1], vel[2], type, dff, 1, partials);
   else k_stress_partial<<<nb, 256, 0, stream>>>(n, pos[0], pos[1], pos[2], frc[0], frc[1], frc[2], type, dff, 0, partials);
-  k_stress_final<<<1, 384, 0, stream>>>(nb, partials, scal + 48);
+  k_stress_final<<<1, 384, 0, stream>>>(nb, partials, scal + SCAL_ASTR);
 }
 
 // The charge-free part of FORCE on the third stream (engine.h: bond_stream): bond orders, every bonded term, the assembly of the bonded forces, next
@@ -152,59 +152,57 @@ __global__ void k_add_force3(int n, const double *__restrict__ ax, const double 
 // x, y, z of the cell-sorted packed copy, and WRITES frc, fsort, the bond accumulators and pe; the main stream meanwhile writes q of the ghosts, the
 // w component of sorted_xyzi (k_sorted_charge) and fnb.  No kernel of the bonded chain may decode sorted_xyzi[].w or read q.
 void Engine::bonded_chain_begin() {
-  RX_HIP(hipMemsetAsync(scal + 32, 0, sizeof(double) * 16, stream));     // the energy accumulators: both chains add to them
+  RX_HIP(hipMemsetAsync(scal + SCAL_PE, 0, sizeof(double) * SCAL_PE_N, stream));     // the energy accumulators: both chains add to them
   RX_HIP(hipEventRecord(ev_fork, stream));
   RX_HIP(hipStreamWaitEvent(bond_stream, ev_fork, 0));
-  std::swap(stream, bond_stream);
-  try {
-    { const bool kt = kt_begin(&st.ms_k_bondorder, &st.ms_bo); bond_orders(); kt_end(kt); }
-    const KtPair t_bonded = outer_begin(&st.ms_bonded);
+  {
+    StreamSwap on_bond(stream, bond_stream);           // (declared first: the timers below end on bond_stream, then the streams swap back)
+    { Timed kt(this, &st.ms_k_bondorder, &st.ms_bo); bond_orders(); }
+    TimedSection t_bonded(this, &st.ms_bonded);
     bonded_energies();
-    { const bool kt = kt_begin(&st.ms_k_assemble); assemble_forces(); kt_end(kt); }
-    outer_end(t_bonded);
-  } catch (...) { std::swap(stream, bond_stream); throw; }
-  std::swap(stream, bond_stream);
+    { Timed kt(this, &st.ms_k_assemble); assemble_forces(); }
+  }
   RX_HIP(hipEventRecord(ev_bond, bond_stream));
 }
 
 void Engine::force(bool defer_host_read, bool observe_energy) {
   if (!atoms_set) throw EngineError(RXMD_E_STATE, "atoms were never set");
-  const KtPair t_force = outer_begin(&st.ms_force);
+  TimedSection t_force(this, &st.ms_force);
   if (!lists_valid) build_ghosts_and_lists();
-  double *pe_d = scal + 32;
+  double *pe_d = scal + SCAL_PE;
   if (bond_overlap()) {
     // (Starting the chain earlier, behind the list build and underneath the CG iterations, was measured: the matrix passes that share the GPU with it
     //  slow down by exactly what the chain saves -- 48.2-48.5 against 48.0-48.7 ms per step, the pass 1.02 against 0.82 ms -- so it starts here.)
     bonded_chain_begin();
     if (multi()) { on_comm_stream([&] { charge_halo(); }); join_comm_stream(); } else charge_halo();
-    { const bool kt = kt_begin(&st.ms_k_nonbond, &st.ms_nonbond); nonbonded(true, observe_energy); kt_end(kt); }        // pot.F90:48-52
-    { const bool kt = kt_begin(&st.ms_bond_exposed); RX_HIP(hipStreamWaitEvent(stream, ev_bond, 0)); kt_end(kt); }   // what of the bonded chain ENbond did not hide
+    { Timed kt(this, &st.ms_k_nonbond, &st.ms_nonbond); nonbonded(true, observe_energy); }        // pot.F90:48-52
+    { Timed kt(this, &st.ms_bond_exposed); RX_HIP(hipStreamWaitEvent(stream, ev_bond, 0)); }   // what of the bonded chain ENbond did not hide
     st.bond_overlap = 1;
     k_add_force3<<<nblk(N, 256), 256, 0, stream>>>(N, fnb[0], fnb[1], fnb[2], frc[0], frc[1], frc[2]);
     accumulate_stress(false);                            // pot.F90:65-72, before the ghost forces are folded back
-    { const bool kt = kt_begin(&st.ms_fold); fold_ghost_forces(); kt_end(kt); }
-    RX_HIP(hipMemcpyAsync(h_scal + 32, pe_d, sizeof(double) * 16, hipMemcpyDeviceToHost, stream));
-    outer_end(t_force);
+    { Timed kt(this, &st.ms_fold); fold_ghost_forces(); }
+    RX_HIP(hipMemcpyAsync(h_scal + H_SCAL_PE, pe_d, sizeof(double) * SCAL_PE_N, hipMemcpyDeviceToHost, stream));
+    t_force.end();
     force_pending = true;
     if (!defer_host_read) finish_force();
     return;
   }
-  RX_HIP(hipMemsetAsync(pe_d, 0, sizeof(double) * 16, stream));
+  RX_HIP(hipMemsetAsync(pe_d, 0, sizeof(double) * SCAL_PE_N, stream));
   // the ghost-charge halo needs nothing from the bond orders and they need no charges: on a multi-rank run the exchange goes to
   // the second stream and meets the main stream again in front of the nonbonded kernel
   if (multi()) on_comm_stream([&] { charge_halo(); }); else charge_halo();
-  { const bool kt = kt_begin(&st.ms_k_bondorder, &st.ms_bo); bond_orders(); kt_end(kt); }
+  { Timed kt(this, &st.ms_k_bondorder, &st.ms_bo); bond_orders(); }
   if (multi()) join_comm_stream();
-  { const bool kt = kt_begin(&st.ms_k_nonbond, &st.ms_nonbond); if (ff.pqeq) nonbonded_pqeq(); else nonbonded(false, observe_energy); kt_end(kt); }     // pot.F90:48-52
-  const KtPair t_bonded = outer_begin(&st.ms_bonded);
+  { Timed kt(this, &st.ms_k_nonbond, &st.ms_nonbond); if (ff.pqeq) nonbonded_pqeq(); else nonbonded(false, observe_energy); }     // pot.F90:48-52
+  TimedSection t_bonded(this, &st.ms_bonded);
   bonded_energies();
   if (ff.pqeq) efield_force();                         // pot.F90:61, before ForceBondedTerms
-  { const bool kt = kt_begin(&st.ms_k_assemble); assemble_forces(); kt_end(kt); }
+  { Timed kt(this, &st.ms_k_assemble); assemble_forces(); }
   accumulate_stress(false);                            // pot.F90:65-72, before the ghost forces are folded back
-  { const bool kt = kt_begin(&st.ms_fold); fold_ghost_forces(); kt_end(kt); }
-  outer_end(t_bonded);
-  RX_HIP(hipMemcpyAsync(h_scal + 32, pe_d, sizeof(double) * 16, hipMemcpyDeviceToHost, stream));
-  outer_end(t_force);
+  { Timed kt(this, &st.ms_fold); fold_ghost_forces(); }
+  t_bonded.end();
+  RX_HIP(hipMemcpyAsync(h_scal + H_SCAL_PE, pe_d, sizeof(double) * SCAL_PE_N, hipMemcpyDeviceToHost, stream));
+  t_force.end();
   force_pending = true;
   if (!defer_host_read) finish_force();
 }
@@ -215,7 +213,7 @@ void Engine::finish_force() {
   force_pending = false;
   sync_stream();
   pe[0] = 0.0;
-  for (int k = 1; k < 14; ++k) { pe[k] = h_scal[32 + k]; pe[0] += pe[k]; }   // PE(0)=sum(PE(1:13)), main.F90:236
+  for (int k = 1; k < 14; ++k) { pe[k] = h_scal[H_SCAL_PE + k]; pe[0] += pe[k]; }   // PE(0)=sum(PE(1:13)), main.F90:236
   collect_timers();
   if (!std::isfinite(pe[0])) throw EngineError(RXMD_E_NAN, "non-finite potential energy (degenerate geometry?)");
 }
@@ -391,27 +389,17 @@ __global__ void k_scale_velocities(int n, const ScaleArgs *__restrict__ ap, cons
 void Engine::kinetic_and_charge(double &ke, double &qsum) {
   const int nb = 240;
   k_ke_qsum<<<nb, 256, 0, stream>>>(N, type, dff, vel[0], vel[1], vel[2], q, partials);
-  k_sum6<<<1, 64, 0, stream>>>(nb, partials, scal + 56);
-  RX_HIP(hipMemcpyAsync(h_scal + 56, scal + 56, sizeof(double) * 2, hipMemcpyDeviceToHost, stream));
+  k_sum6<<<1, 64, 0, stream>>>(nb, partials, scal + SCAL_PRINTE);
+  RX_HIP(hipMemcpyAsync(h_scal + H_SCAL_PRINTE, scal + SCAL_PRINTE, sizeof(double) * 2, hipMemcpyDeviceToHost, stream));
   sync_stream();
-  ke = h_scal[56]; qsum = h_scal[57];
+  ke = h_scal[H_SCAL_PRINTE]; qsum = h_scal[H_SCAL_PRINTE + 1];
 }
 
 // the per-type sums of the residents' velocities, summed over all ranks, in tsum (device memory) -- no host wait with the native transport
 void Engine::type_sums_device() {
   k_type_sums<<<TSUM_BLOCKS, 256, 0, stream>>>(N, ff.nso, type, dff, vel[0], vel[1], vel[2], partials);
   k_type_sums_final<<<1, 128, 0, stream>>>(TSUM_BLOCKS, ff.nso, partials, tsum);
-  if (nprocs > 1) {                                                  // MPI_ALLREDUCE, main.F90:699,738,783
-    const int n = 6 * (ff.nso + 1);
-    const bool kt = kt_begin(&st.ms_allreduce, nullptr, &st.allreduce_calls);
-    struct End { Engine *e; bool kt; ~End() { e->kt_end(kt); } } end_{this, kt};
-    if (nccl) { rccl_allreduce_dev(tsum, n); return; }               // in stream order
-    if (!has_comm || !comm.allreduce_sum) throw EngineError(RXMD_E_COMM, "vprocs > 1 needs a transport: call rxmd_hip_set_comm or rxmd_hip_comm_init_rccl first");
-    RX_HIP(hipMemcpyAsync(h_scal + 192, tsum, sizeof(double) * n, hipMemcpyDeviceToHost, stream));      // a host transport (MPI callbacks): its all-reduce IS a host call
-    sync_stream();
-    if (comm.allreduce_sum(comm.ctx, h_scal + 192, n)) throw EngineError(RXMD_E_COMM, "allreduce callback failed");
-    RX_HIP(hipMemcpyAsync(tsum, h_scal + 192, sizeof(double) * n, hipMemcpyHostToDevice, stream));
-  }
+  if (nprocs > 1) allreduce_device(tsum, 6 * (ff.nso + 1), H_SCAL_TSUM);   // MPI_ALLREDUCE, main.F90:699,738,783
 }
 
 void Engine::thermostat(int mdmode, double treq_K, double vsfact, double gke) {
@@ -449,7 +437,7 @@ void Engine::remove_momentum() {                  // LinearMomentum (main.F90:76
 
 // ------------------------------------------------------------------------------------------------
 // Berendsen barostat (rxmd_hip_set_barostat; no counterpart in the reference, whose box is fixed after INITSYSTEM).  On a coupling step:
-//   k_bar_head  at the head of the step: the stress accumulators astr (scal[48..53]) copied aside (scal[SCAL_BAR_HEAD..+6), behind the CG snapshot slots: QEq runs between head and sums) -- astr itself is left as
+//   k_bar_head  at the head of the step: the stress accumulators astr (scal + SCAL_ASTR) copied aside (scal[SCAL_BAR_HEAD..+6), behind the CG snapshot slots: QEq runs between head and sums) -- astr itself is left as
 //               it is, so rxmd_hip_get_energy reads and resets exactly what it does without a barostat
 //   k_bar_sums  behind the second half-kick: the step's own sums = astr - head (virial of this step's FORCE, ENbond's pair correction
 //               included, + m v v of this step), scal[SCAL_BAR_STEP..+6); then summed over the ranks (RCCL in stream order, or the host all-reduce)
@@ -480,24 +468,13 @@ __global__ void k_bar_mu(const double *__restrict__ step6, BarArgs a, double *ou
 
 void Engine::barostat_couple() {
   double *head6 = scal + SCAL_BAR_HEAD, *step6 = scal + SCAL_BAR_STEP;
-  k_bar_sums<<<1, 64, 0, stream>>>(scal + 48, head6, step6);
-  if (nprocs > 1) {
-    const bool kt = kt_begin(&st.ms_allreduce, nullptr, &st.allreduce_calls);
-    struct End { Engine *e; bool kt; ~End() { e->kt_end(kt); } } end_{this, kt};
-    if (nccl) rccl_allreduce_dev(step6, 6);                            // in stream order
-    else {
-      if (!has_comm || !comm.allreduce_sum) throw EngineError(RXMD_E_COMM, "vprocs > 1 needs a transport: call rxmd_hip_set_comm or rxmd_hip_comm_init_rccl first");
-      RX_HIP(hipMemcpyAsync(h_scal + 304, step6, sizeof(double) * 6, hipMemcpyDeviceToHost, stream));
-      sync_stream();
-      if (comm.allreduce_sum(comm.ctx, h_scal + 304, 6)) throw EngineError(RXMD_E_COMM, "allreduce callback failed");
-      RX_HIP(hipMemcpyAsync(step6, h_scal + 304, sizeof(double) * 6, hipMemcpyHostToDevice, stream));
-    }
-  }
+  k_bar_sums<<<1, 64, 0, stream>>>(scal + SCAL_ASTR, head6, step6);
+  if (nprocs > 1) allreduce_device(step6, 6, H_SCAL_BAR_REDUCE);
   BarArgs a{};
   a.mode = bar_mode; a.axes = bar_axes;
   for (int k = 0; k < 3; ++k) a.p0[k] = bar_p0[k];
   a.rate = bar_every * cfg.dt_fs / bar_tau; a.B = bar_B; a.max_strain = bar_max; a.volume = box.volume;   // the volume the forces of this step were computed at
-  double *out9 = h_scal + 288;                                         // [288, 297) of the pinned block: p6, mu
+  double *out9 = h_scal + H_SCAL_BAR_OUT;                              // p6, mu
   k_bar_mu<<<1, 64, 0, stream>>>(step6, a, out9);
   sync_stream();
   for (int c = 0; c < 6; ++c) bar_p6[c] = out9[c];
@@ -516,12 +493,11 @@ void Engine::step(int nsteps) {
   // The event pairs of the per-kernel timers (rxmd_stats.ms_k_*, ms_bo, ms_nonbond, ...) cost the stream ~5 us per event, ~12 pairs per step.  A call of 8
   // steps or more times them on every 4th step only and counts their milliseconds four-fold (bench.py's per-kernel table is such an average; the kernels
   // do the same work every step); shorter calls time every step.  The sections (QEq, FORCE, list build) keep their pair on every step.
-  kt_every = nsteps >= 8 ? 4 : 1;
-  struct Restore { Engine *e; ~Restore() { e->kt_every = 1; e->kt_phase = 0; } } restore_{this};
+  Restore<int> every(kt_every, nsteps >= 8 ? 4 : 1), phase(kt_phase);
   for (int s = 0; s < nsteps; ++s) {
     kt_phase = s;
     const bool couple = bar_mode != 0 && (step_count + 1) % bar_every == 0;   // barostat: every `every`-th step (mode 0: nothing new is launched)
-    if (couple) k_bar_head<<<1, 64, 0, stream>>>(scal + 48, scal + SCAL_BAR_HEAD);
+    if (couple) k_bar_head<<<1, 64, 0, stream>>>(scal + SCAL_ASTR, scal + SCAL_BAR_HEAD);
     if (cfg.efield_dir != 0) {             // always correct the linear momentum when an electric field is applied (main.F90:70-71)
       k_kick<<<nblk(N, 256), 256, 0, stream>>>(N, dff, dt, Lex_w2, type, vel[0], vel[1], vel[2], frc[0], frc[1], frc[2], q, qsfp, qsfv);
       k_lex_drift<<<nblk(N, 256), 256, 0, stream>>>(N, dt, qsfp, qsfv);
@@ -529,7 +505,7 @@ void Engine::step(int nsteps) {
       k_drift<<<nblk(N, 256), 256, 0, stream>>>(N, dt, vel[0], vel[1], vel[2], pos[0], pos[1], pos[2]);
     } else
       k_kick_drift<<<nblk(N, 256), 256, 0, stream>>>(N, dff, dt, Lex_w2, type, vel[0], vel[1], vel[2], frc[0], frc[1], frc[2], pos[0], pos[1], pos[2], q, qsfp, qsfv);
-    { const bool kt = kt_begin(&st.ms_migrate); migrate(); kt_end(kt); }                                 // main.F90:75
+    { Timed kt(this, &st.ms_migrate); migrate(); }                                 // main.F90:75
     const int qs = cfg.qstep > 0 ? cfg.qstep : 1;
     if (step_count % qs == 0) qeq();                                     // main.F90:77-83
     force(true, s == nsteps - 1);                                        // main.F90:84 (energies read once, behind the last step: only that step forms ENbond's)

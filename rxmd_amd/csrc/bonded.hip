@@ -861,6 +861,7 @@ __global__ void __launch_bounds__(64 * WPB, E4B_MINB) k_e4b(int N, DevFF ff, con
         }
         if (t0 != 0.0 || t1 != 0.0 || t2 != 0.0) {
           const double F0 = 0.5 * (o[1] + fself.x), F1 = 0.5 * (o[2] + fself.y), F2 = 0.5 * (o[3] + fself.z);
+          static_assert(SCAL_ASTR == SCAL_PE + 16, "pe = scal + SCAL_PE: the stress accumulators astr are pe + 16 .. pe + 21");
           if (t0 != 0.0) { atomicAdd(pe + 16, t0 * F0); atomicAdd(pe + 21, t0 * F1); }     // xx, xy
           if (t1 != 0.0) { atomicAdd(pe + 17, t1 * F1); atomicAdd(pe + 19, t1 * F2); }     // yy, yz
           if (t2 != 0.0) { atomicAdd(pe + 18, t2 * F2); atomicAdd(pe + 20, t2 * F0); }     // zz, zx
@@ -1336,11 +1337,11 @@ __global__ void k_add_sorted3(int G, const int *__restrict__ perm, const double 
 }
 
 void Engine::bonded_energies() {
-  double *pe_d = scal + 32;   // 14 energy accumulators live behind the CG scalars
+  double *pe_d = scal + SCAL_PE;   // 14 energy accumulators live behind the CG scalars
   k_ebond_terms<<<nblk(nbonds_res, 256), 256, 0, stream>>>(nbonds_res, dff, bown, nbr, btype, type, gid, bo0, bo1, bo2, bo3, delta, deltalp, cf1, cf2, cf3, ecoa, bt1, bt2, pe_d);
   k_elnpr_atoms<<<nblk(N, 256), 256, 0, stream>>>(N, dff, boff, type, bt1, bt2, delta, deltalp, dDlp, ecoef, pe_d);
   k_elnpr_bonds<<<nblk(nbonds_res, 256), 256, 0, stream>>>(nbonds_res, dff, bown, nbr, btype, type, bo2, bo3, delta, deltalp, dDlp, ecoef, cf1, cf2, cf3, cdn);
-  const bool kt3 = kt_begin(&st.ms_k_e3b);
+  Timed kt3(this, &st.ms_k_e3b);
   // the work-queue form (k_e3q) when the angle tables fit LDS: sixteen centre atoms per wavefront where no bond list of the step is longer than 12
   // (h_err[2]: the longest list, 0 up to 8), eight up to 24, four beyond
   if (opt.e3b_queue != 0 && dff.n1 <= 8 && dff.nvaty <= 255) {
@@ -1358,7 +1359,7 @@ void Engine::bonded_energies() {
     k_e3b<<<nblk(N, 256), 256, 4 * 5 * E3B_CAP * sizeof(double), stream>>>(N, dff, boff, nbr, btype, type, pos[0], pos[1], pos[2], bo0, bo2, bo3, delta, nlp, dDlp, epen, ecoa, cf1, cf2, cf3, cdn, fnx, fny, fnz,
                                           cds, frc[0], frc[1], frc[2], pe_d);
   RX_HIP(hipGetLastError());                       // 70 KB of dynamic LDS: a refused launch must not pass for "no valence angles"
-  kt_end(kt3);
+  kt3.end();
   BoxImg bx;
   for (int a = 0; a < 3; ++a) { for (int c = 0; c < 3; ++c) { bx.H[3 * a + c] = box.H[a][c]; bx.Hi[3 * a + c] = box.Hi[a][c]; } bx.L[a] = box.lat[a]; }
   bx.ortho = grid.ortho; bx.probe = 0;
@@ -1370,7 +1371,7 @@ void Engine::bonded_energies() {
   // for most groups and is slower than the default there, 3.69 against 3.47 ms), four atoms x 16 slots (16, needs lists <= 15)
   const int want = static_cast<int>(opt.e4b_slots);
   const bool narrow = h_err[2] <= 15 && want != 32 && want != 4;
-  const bool kt4 = kt_begin(&st.ms_k_e4b);
+  Timed kt4(this, &st.ms_k_e4b);
   bool once = opt.e4b_once != 0;
   const int TW = (std::max(h_err[2], 8) + 3) & ~3;                          // columns of the k-l delivery table: the longest bond list of the step (h_err[2]: 0 when none is longer than 8)
   if (once) {
@@ -1414,8 +1415,8 @@ void Engine::bonded_energies() {
     k_e4b_deliver<<<nblk(nbonds, 256), 256, 0, stream>>>(nbonds, TW, e4b_t, reinterpret_cast<unsigned *>(e4b_flag), cf1, fnx, fny, fnz);
     e4b_dirty = false;
   }
-  kt_end(kt4);
-  const bool kth = kt_begin(&st.ms_k_ehb);
+  kt4.end();
+  Timed kth(this, &st.ms_k_ehb);
   if (ehb_donor_types != 0u) {                    // (a force field without a hydrogen-bond row for hydrogen = type 2 has no donors: water, pot.F90:595)
     const int region_cap = (nblk(N, 256) + EHB_REGIONS - 1) / EHB_REGIONS * 256;            // every atom of the workgroups of a region a donor: cannot overflow
     if (static_cast<size_t>(region_cap) * EHB_REGIONS > ehb_don_cap) throw EngineError(RXMD_E_STATE, "hydrogen-bond donor list: capacity");
@@ -1447,7 +1448,6 @@ void Engine::bonded_energies() {
 #endif
     k_add_sorted3<<<nblk(G, 256), 256, 0, stream>>>(G, perm, fsort[0], fsort[1], fsort[2], frc[0], frc[1], frc[2]);
   }
-  kt_end(kth);
 }
 
 }  // namespace rxmd

@@ -62,8 +62,6 @@ void *pinned_alloc(size_t bytes, bool coherent_mapped) {
 void pinned_free(void *p) { if (p) (void)hipHostFree(p); }
 
 // ---- the table ------------------------------------------------------------------------------------------------------------------------
-constexpr size_t H_SCAL_DOUBLES = 320;   // pinned mirror of the scalars: [0,64) as the device block; [64,192) the two slots of the run-ahead CG loop (qeq.hip); [192,288) the per-type sums of a host transport; [288,310) the barostat's; [310,316) H_SCAL_EVAL_VIRIAL
-static_assert(H_SCAL_EVAL_VIRIAL + 6 <= H_SCAL_DOUBLES, "the virial of the device-array evaluate call lies inside the pinned mirror");
 constexpr size_t H_ERR_INTS = 32;        // 16 ints of the device error words + 16 (h_cnt) for the counts the host waits for
 constexpr size_t H_SEG_INTS = 32;        // totals of the 26-segment ghost build
 constexpr size_t H_PUB_WORDS = 32;       // words published through pinned memory (sequence number << 32 | value, pinned_wait)
@@ -171,7 +169,7 @@ void Engine::declare_buffers() {
   b.add(hess32, G_LIST10, Dim::List10, 1, 0, P, whole, BUF_QEQ_F32);      // the matrix values as REAL(4), only while set_qeq_precision(32) is in force
   b.add(partials, G_PARTIALS, Dim::Cap, 1, 1024, P, whole);   // + the 128 x 4 first-level sums of k_reduce_fused, behind the per-workgroup partials at a fixed offset
   b.add(scal, G_SETUP, Dim::Fixed, 0, SCAL_N, Z, never, res);
-  b.add_pinned(h_scal, G_SETUP, H_SCAL_DOUBLES, true);        // coherent: the update kernel's tail stores the CG snapshot into it and the host polls it
+  b.add_pinned(h_scal, G_SETUP, H_SCAL_N, true);        // coherent: the update kernel's tail stores the CG snapshot into it and the host polls it
   b.add(tsum, G_SETUP, Dim::Fixed, 0, 128, Z, never);
   b.add_raw(reinterpret_cast<void **>(&sargs), sizeof(double), G_SETUP, Dim::Fixed, 0, 32, Z, never);   // room of 32 doubles for the ScaleArgs of assemble.hip
   b.add(d_err, G_SETUP, Dim::Fixed, 0, 16, Z, never);

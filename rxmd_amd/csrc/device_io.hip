@@ -126,14 +126,14 @@ void Engine::evaluate_device(int natoms, const long long *gid_d, const int *type
   for (int a = 0; a < 3; ++a) RX_HIP(hipMemsetAsync(frc[a], 0, sizeof(double) * NB, stream));
   const int q_mode = q_in_d ? 1 : (warm_n == natoms ? 0 : 2);
   k_ingest_device<<<nblk(natoms, 256), 256, 0, stream>>>(natoms, ff.nso, B, pos3_d, type_d, gid_d, q_in_d, q_mode, pos[0], pos[1], pos[2], vel[0], vel[1], vel[2],
-                                                          q, qsfp, qsfv, type, gid, d_err, scal + 48, scal + SCAL_EVAL_HEAD);
+                                                          q, qsfp, qsfv, type, gid, d_err, scal + SCAL_ASTR, scal + SCAL_EVAL_HEAD);
   N = natoms; G = natoms;
   atoms_set = true; lists_valid = false; ghosts_valid = false;
   atype_resid = 0.0;
   st.natoms = N;
   qeq();                                           // (isQEq = 0: returns at once, the charges are the caller's)
   force(true);                                     // the list build in front of either reports a type outside the ffield (RXMD_E_ARG)
-  k_egress_device<<<nblk(natoms, 256), 256, 0, stream>>>(natoms, frc[0], frc[1], frc[2], q, f3_d, q_out_d, scal + 48, scal + SCAL_EVAL_HEAD, h_scal + H_SCAL_EVAL_VIRIAL);
+  k_egress_device<<<nblk(natoms, 256), 256, 0, stream>>>(natoms, frc[0], frc[1], frc[2], q, f3_d, q_out_d, scal + SCAL_ASTR, scal + SCAL_EVAL_HEAD, h_scal + H_SCAL_EVAL_VIRIAL);
   RX_HIP(hipEventRecord(ev_io_out, stream));
   RX_HIP(hipStreamWaitEvent(user, ev_io_out, 0));
   finish_force();                                  // the host wait of the call: energies, NaN trap

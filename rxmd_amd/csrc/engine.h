@@ -106,12 +106,32 @@ struct RefMesh {
 
 constexpr int WAVE = 64;
 
-// the device scalar block `scal` (double): [0, S_COUNT) CG scalars (spmv_kernels.h), [32, 48) energies, [48, 54) the stress accumulators astr,
-// [56, 62) PRINTE's sums, [64, 72) staging of the host all-reduce, [128, 192) the two CG snapshot slots (S_SNAP), and the barostat's own
-// 6-vectors behind them: the step-head copy of astr and the step's sums.  [72, 78): astr as the device-array evaluate call found it (device_io.hip)
-constexpr int SCAL_BAR_HEAD = 192, SCAL_BAR_STEP = 200, SCAL_N = 208;
-constexpr int SCAL_EVAL_HEAD = 72;
-constexpr int H_SCAL_EVAL_VIRIAL = 310;   // pinned mirror h_scal: the six virial sums of the device-array evaluate call (the egress kernel stores them there)
+// ---- the two scalar blocks, in doubles: `scal` in device memory and its pinned host mirror `h_scal`.  Every slot of either is named HERE. ----
+// The CG scalars sit at the head of both (the host copies [0, S_COUNT) across as one piece); S_RAW0..7: the sums a reduction leaves for the algebra
+enum { S_MU = 0, S_LMIN_S, S_LMIN_T, S_GOLD_S, S_GOLD_T, S_GNEW_S, S_GNEW_T, S_EST, S_GH_S, S_GH_T, S_HSH_S, S_HSH_T, S_SSUM, S_TSUM, S_BETA_S, S_BETA_T, S_RAW0, S_RAW1, S_RAW2, S_RAW3, S_RAW4, S_RAW5, S_RAW6, S_RAW7, S_STOP, S_STOP1, S_TOL, S_COUNT };
+constexpr int SCAL_CG_N = 32, SCAL_N = 208, H_SCAL_N = 320;   // the range of the CG scalars (a QEq call clears it in front of its start vector) ; doubles of either block
+constexpr int SCAL_PE = 32, SCAL_PE_N = 16, H_SCAL_PE = 32;   // the energy accumulators PE(0:13) of FORCE, and where the host reads them
+constexpr int SCAL_ASTR = 48;                                 // the six stress accumulators astr: ENbond and the torsions reach them as pe + 16 (asserted next to those kernels)
+constexpr int SCAL_PRINTE = 56, H_SCAL_PRINTE = 56;           // PRINTE's sums: kinetic energy, charge
+constexpr int SCAL_REDUCE = 64, H_SCAL_REDUCE = 48;           // staging: of allreduce_host in device memory ; of the host all-reduce of scal[S_RAW0..] in pinned memory
+constexpr int SCAL_EVAL_HEAD = 72, H_SCAL_EVAL_VIRIAL = 310;  // the device-array evaluate call (device_io.hip): astr as it found it ; its six virial sums (the egress kernel stores them there)
+constexpr int H_SCAL_TOL = 60;                                // QEq_tol on its way to scal[S_TOL]
+constexpr int S_SNAP = 128, S_SNAP_STRIDE = 32;               // scal[S_SNAP + 32 p ..]: snapshot of the scalars of an iteration of parity p (scalar_algebra stage 6)
+constexpr int H_SCAL_SNAP = 64, H_SNAP_STRIDE = 64, H_SNAP_SEQ = 63;   // the same in pinned memory for the run-ahead CG loop, its sequence number in word 63: the update kernel's tail stores it, the host polls it
+constexpr int H_SCAL_TSUM = 192, H_SCAL_TSUM_N = 6 * 16;      // per-type sums through a host transport
+constexpr int SCAL_BAR_HEAD = 192, SCAL_BAR_STEP = 200, H_SCAL_BAR_OUT = 288, H_SCAL_BAR_REDUCE = 304;   // the barostat: step-head copy of astr, the step's sums ; pressure tensor and factors (p6, mu), staging of its all-reduce
+struct ScalSlot { int at, n; };
+constexpr bool slots_disjoint_within(const ScalSlot *s, int count, int total) {
+  for (int i = 0; i < count; ++i) for (int j = 0; j <= i; ++j)
+    if (s[i].at < 0 || s[i].n <= 0 || s[i].at + s[i].n > total || (j < i && s[i].at < s[j].at + s[j].n && s[j].at < s[i].at + s[i].n)) return false;
+  return true;
+}
+constexpr ScalSlot SCAL_SLOTS[] = {{0, SCAL_CG_N}, {SCAL_PE, SCAL_PE_N}, {SCAL_ASTR, 6}, {SCAL_PRINTE, 6}, {SCAL_REDUCE, 8}, {SCAL_EVAL_HEAD, 6}, {S_SNAP, 2 * S_SNAP_STRIDE}, {SCAL_BAR_HEAD, 6}, {SCAL_BAR_STEP, 6}};
+constexpr ScalSlot H_SCAL_SLOTS[] = {{0, SCAL_CG_N}, {H_SCAL_PE, SCAL_PE_N}, {H_SCAL_REDUCE, 8}, {H_SCAL_PRINTE, 2}, {H_SCAL_TOL, 1}, {H_SCAL_SNAP, 2 * H_SNAP_STRIDE}, {H_SCAL_TSUM, H_SCAL_TSUM_N}, {H_SCAL_BAR_OUT, 9}, {H_SCAL_BAR_REDUCE, 6}, {H_SCAL_EVAL_VIRIAL, 6}};
+static_assert(slots_disjoint_within(SCAL_SLOTS, sizeof(SCAL_SLOTS) / sizeof(ScalSlot), SCAL_N), "two slots of the device scalar block overlap, or one leaves the block");
+static_assert(slots_disjoint_within(H_SCAL_SLOTS, sizeof(H_SCAL_SLOTS) / sizeof(ScalSlot), H_SCAL_N), "two slots of the pinned scalar block overlap, or one leaves the block");
+static_assert(S_COUNT <= SCAL_CG_N && S_COUNT <= S_SNAP_STRIDE && S_COUNT <= H_SNAP_SEQ, "the CG scalars fit their range and either snapshot slot");
+static_assert(S_RAW0 + 8 <= S_STOP, "the eight raw sums stay inside the CG scalars");
 
 // XCD-aware workgroup order: the dispatcher deals consecutive workgroup ids round-robin to the 8 XCDs (each with its own L2),
 // so without a remap every L2 sees rows from all over the box and re-fetches the whole gather vector.  With it the
@@ -196,6 +216,19 @@ struct Buffers {
   void restore_residents(const std::vector<std::vector<char>> &h);
 };
 constexpr size_t EHB_DON_EXTRA = 64 * 256 + 256;   // donor list beyond one entry per row: 64 sub-lists (bonded.hip EHB_REGIONS) padded to 256
+
+// engine state that a block changes and every way out of it, an exception included, puts back
+template <class T> struct Restore {                   // a value: what `ref` held when the block was entered
+  T &ref; const T old;
+  explicit Restore(T &r) : ref(r), old(r) {}
+  Restore(T &r, T inside) : ref(r), old(r) { r = inside; }
+  ~Restore() { ref = old; }
+};
+struct StreamSwap {                                   // the engine's stream against another one; `inside` (optional) is true for as long
+  hipStream_t &a, &b; bool *inside;
+  StreamSwap(hipStream_t &a_, hipStream_t &b_, bool *inside_ = nullptr) : a(a_), b(b_), inside(inside_) { std::swap(a, b); if (inside) *inside = true; }
+  ~StreamSwap() { if (inside) *inside = false; std::swap(a, b); }
+};
 
 struct ScaleArgs;
 struct WinPassArgs; struct RowPassArgs;   // the operands of the two matrix-pass kernels (spmv_kernels.h)
@@ -300,11 +333,7 @@ struct Engine {
   template <class F> void on_comm_stream(F &&body) {          // body runs with `stream` == comm_stream, after everything queued on the main stream so far
     RX_HIP(hipEventRecord(ev_main, stream));
     RX_HIP(hipStreamWaitEvent(comm_stream, ev_main, 0));
-    std::swap(stream, comm_stream);
-    in_comm_region = true;
-    try { body(); } catch (...) { in_comm_region = false; std::swap(stream, comm_stream); throw; }
-    in_comm_region = false;
-    std::swap(stream, comm_stream);
+    { StreamSwap on_comm(stream, comm_stream, &in_comm_region); body(); }
     RX_HIP(hipEventRecord(ev_comm, comm_stream));
   }
   bool in_comm_region = false;
@@ -316,7 +345,7 @@ struct Engine {
   bool bond_overlap() const { return bond_stream != nullptr && !ff.pqeq; }
   void bonded_chain_begin();
   // main stream waits for what on_comm_stream queued; the wait itself is timed: that is the part of the exchange the compute did not hide
-  void join_comm_stream() { const bool kt = kt_begin(&st.ms_halo_exposed, nullptr, nullptr, 2); RX_HIP(hipStreamWaitEvent(stream, ev_comm, 0)); kt_end(kt); }
+  void join_comm_stream() { Timed kt(this, &st.ms_halo_exposed, nullptr, nullptr, 2); RX_HIP(hipStreamWaitEvent(stream, ev_comm, 0)); }
   hipEvent_t ev[8] = {};
   std::vector<double> last_atype, last_pos[3];    // what the array-shaped entry points uploaded last (capi.hip)
   std::vector<double> lex_p, lex_v; bool lex_pending = false;   // qsfp/qsfv handed over by rxmd_hip_put_lex for the next array-shaped QEq/PQEq
@@ -364,15 +393,15 @@ struct Engine {
   double qeq_start(const CgCall &c);                 // gradient, Est and first direction of the start vector -> Est (0 when the run-ahead loop will read it later)
   int qeq_runahead(const CgCall &c, double &Est);    // the two CG loops -> iterations done
   int qeq_host_paced(const CgCall &c, double &Est);
-  struct KtPair;
-  void qeq_finish(int it, double Est, KtPair t_qeq); // shells, iteration statistics, the call's timer, once: the placement search
+  struct TimedSection;
+  void qeq_finish(int it, double Est, TimedSection &t_qeq); // shells, iteration statistics, the call's timer, once: the placement search
   // observe_energy = false (Engine::step, every step but the last of a call): nothing reads this FORCE's energies -- ENbond skips its pair and self
   // energies, PE(11:13) stay 0 in the block that the next observed FORCE overwrites.  Forces and the virial (astr accumulates over steps) are untouched.
   void force(bool defer_host_read = false, bool observe_energy = true);   // defer: the energies stay in the pinned buffer until finish_force() (step(): no host wait between FORCE and the next step)
   void finish_force();
   bool force_pending = false;
   // run-ahead CG loop (qeq.hip): the scalars of an iteration reach the host as a snapshot the update kernel's tail writes straight into pinned host memory
-  // (h_scal + 64 + 64 * parity, sequence number in word 63), no copy, no event: the host polls the sequence number
+  // (h_scal + H_SCAL_SNAP + H_SNAP_STRIDE * parity, sequence number in word H_SNAP_SEQ), no copy, no event: the host polls the sequence number
   unsigned long long snap_seq = 0; double snap_expect[2] = {0.0, 0.0};
   void wait_snapshot(int parity, double seq);
   // the matrix pass is timed on a SAMPLE of its launches there (opt.pass_timing_every): sum and count of the timed ones; rxmd_stats.ms_qeq_spmv = average x all launches
@@ -489,6 +518,9 @@ struct Engine {
   bool spin_wait = true;
   void allreduce_scal4(int n = 4);                 // MPI_ALLREDUCE of scal[S_RAW0..n-1] (qeq.hip)
   void allreduce_host(double *buf, int n);         // the same for a host vector (setup paths)
+  // MPI_ALLREDUCE(SUM) of the n doubles at the device address dev, in place: with RCCL in stream order, otherwise through the host callback and the
+  // pinned slot h_scal + h_stage (one host wait); timed into ms_allreduce, as sampled site `site` when >= 0 (engine.hip)
+  void allreduce_device(double *dev, int n, int h_stage, int site = -1);
   void ghost_build_staged();                        // stage by stage: several ranks, or one rank under RXMD_NO_STAGE_PAIRS=1
   void sorted_copy(const double2 *v);               // QCOPY1/QCOPY2 fused with the cell-sorted gather copy -> xs
   void fold_ghost_forces();                         // CPBK
@@ -505,7 +537,7 @@ struct Engine {
   void type_sums_device();        // per-type count / KE / momentum / mass of the residents, all ranks, left in tsum (assemble.hip)
   double *tsum = nullptr; struct ScaleArgs *sargs = nullptr;   // 6 x 16 per-type sums ; the factors of a velocity-scaling action (device memory)
   void assemble_forces();
-  void accumulate_stress(bool kinetic);   // astr(1:6) on the device (scal[48..53])
+  void accumulate_stress(bool kinetic);   // astr(1:6) on the device (scal + SCAL_ASTR)
   void check_device_error(const char *where, bool fetch = true);
   void fetch_device_error();      // the error word and the counts that ride with it -> h_err (one host wait), nothing thrown
   double reduce_partials(int ncomp, int nblocks, double *out);  // host-side helper
@@ -514,48 +546,41 @@ struct Engine {
   // so timing costs no host wait.  A pair adds its milliseconds to up to two rxmd_stats fields.
   struct KtPair { hipEvent_t a = nullptr, b = nullptr; double *dst = nullptr, *dst2 = nullptr; long long *cnt = nullptr; double scale = 1.0; };
   std::vector<KtPair> kt_free, kt_pending;
-  int kt_open = -1;                                // (one nesting level is enough: begin ... end on the stream current at the time)
-  KtPair kt_cur{};
+  KtPair kt_cur{};                                 // the pair of the open Timed (one nesting level is enough: a Timed inside an open one times nothing)
   // site >= 0: a timer that fires in EVERY CG iteration (the all-reduces, the vector halo and the join behind it on several ranks): an event pair between two
   // dependent operations costs the chain ~7 us per event (profiles/r06_ab_pass_events.txt), four pairs per iteration were ~50 us of every iteration of the
   // multi-rank loop.  Such a site is timed on every n-th call only (opt.pass_timing_every) and its milliseconds count n-fold; its calls are all counted.
   unsigned long long kt_site_calls[4] = {0, 0, 0, 0};
   int kt_every = 1, kt_phase = 0;                  // Engine::step: section / kernel timers on every kt_every-th step of a long call, milliseconds counted kt_every-fold
-  bool kt_begin(double *dst, double *dst2 = nullptr, long long *cnt = nullptr, int site = -1) {
-    double scale = 1.0;
-    if (site < 0 && kt_every > 1) {
-      if (cnt) { *cnt += 1; cnt = nullptr; }
-      if (kt_phase % kt_every != 0) return false;
-      scale = static_cast<double>(kt_every);
+  // The scope of one pair: the start event where it is constructed, the end event on the stream current where it ends -- end(), or its destructor on the
+  // way out of the block, by return or by exception -- so that no error path keeps a pair from the pool or leaves kt_cur set.  section: a scope that
+  // CONTAINS Timed scopes (a whole QEq call, a whole FORCE, the list build); timed on every step: the iteration count differs from step to step.
+  struct Timed {
+    Engine &e; const bool section; KtPair p{};
+    Timed(Engine *eng, double *dst, double *dst2 = nullptr, long long *cnt = nullptr, int site = -1, bool section_ = false) : e(*eng), section(section_) {
+      double scale = 1.0;
+      if (!section && site < 0 && e.kt_every > 1) {
+        if (cnt) { *cnt += 1; cnt = nullptr; }
+        if (e.kt_phase % e.kt_every != 0) return;
+        scale = static_cast<double>(e.kt_every);
+      }
+      if (site >= 0) {
+        if (cnt) { *cnt += 1; cnt = nullptr; }
+        const unsigned long long every = static_cast<unsigned long long>(e.opt.pass_timing_every > 1 ? e.opt.pass_timing_every : 1);
+        if ((e.kt_site_calls[site & 3]++ % every) != 0) return;
+        scale = static_cast<double>(every);
+      }
+      if (e.kt_free.empty() || (!section && e.kt_cur.a)) { if (e.kt_free.empty()) ++e.st.timer_pairs_dropped; return; }
+      p = e.kt_free.back(); e.kt_free.pop_back();
+      p.dst = dst; p.dst2 = dst2; p.cnt = cnt; p.scale = scale;
+      hipEventRecord(p.a, e.stream);
+      if (!section) e.kt_cur = p;
     }
-    if (site >= 0) {
-      if (cnt) { *cnt += 1; cnt = nullptr; }
-      const unsigned long long every = static_cast<unsigned long long>(opt.pass_timing_every > 1 ? opt.pass_timing_every : 1);
-      if ((kt_site_calls[site & 3]++ % every) != 0) return false;
-      scale = static_cast<double>(every);
-    }
-    if (kt_free.empty() || kt_cur.a) { if (kt_free.empty()) ++st.timer_pairs_dropped; return false; }
-    kt_cur = kt_free.back(); kt_free.pop_back();
-    kt_cur.dst = dst; kt_cur.dst2 = dst2; kt_cur.cnt = cnt; kt_cur.scale = scale;
-    hipEventRecord(kt_cur.a, stream);
-    return true;
-  }
-  void kt_end(bool open) {
-    if (!open) return;
-    hipEventRecord(kt_cur.b, stream);
-    kt_pending.push_back(kt_cur);
-    kt_cur = KtPair{};
-  }
-  // the same for a section that CONTAINS begin ... end pairs (a whole QEq call, a whole FORCE): its own pair from the pool, handed back explicitly
-  KtPair outer_begin(double *dst) {
-    KtPair p{};
-    if (kt_free.empty()) { ++st.timer_pairs_dropped; return p; }
-    p = kt_free.back(); kt_free.pop_back();
-    p.dst = dst; p.dst2 = nullptr; p.cnt = nullptr; p.scale = 1.0;          // (the sections -- a whole QEq call, FORCE, the list build -- are timed on every step: the iteration count differs from step to step)
-    hipEventRecord(p.a, stream);
-    return p;
-  }
-  void outer_end(KtPair p) { if (!p.a) return; hipEventRecord(p.b, stream); kt_pending.push_back(p); }
+    void end() { if (!p.a) return; hipEventRecord(p.b, e.stream); e.kt_pending.push_back(p); p = KtPair{}; if (!section) e.kt_cur = KtPair{}; }
+    ~Timed() { end(); }
+    Timed(const Timed &) = delete;
+  };
+  struct TimedSection : Timed { TimedSection(Engine *eng, double *dst) : Timed(eng, dst, nullptr, nullptr, -1, true) {} };
   void collect_timers();          // after a stream synchronisation
   void tic(int k) { hipEventRecord(ev[k], stream); }
   double toc(int k0, int k1) { hipEventRecord(ev[k1], stream); hipEventSynchronize(ev[k1]); float ms = 0; hipEventElapsedTime(&ms, ev[k0], ev[k1]); return ms; }

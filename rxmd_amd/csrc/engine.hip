@@ -139,26 +139,29 @@ Engine::~Engine() {
 }
 
 void Engine::allreduce_host(double *buf, int n) {
-  if (nccl && n <= 8) {                       // the usual case: a scalar or two -- the tail of the device scalar block is the staging area
-    double *d = scal + 64;
-    RX_HIP(hipMemcpyAsync(d, buf, sizeof(double) * n, hipMemcpyHostToDevice, stream));
-    rccl_allreduce_dev(d, n);
-    RX_HIP(hipMemcpyAsync(buf, d, sizeof(double) * n, hipMemcpyDeviceToHost, stream));
-    sync_stream();
-    return;
-  }
   if (nccl) {
-    double *d = nullptr;
-    dev_alloc(d, n, Fill::None);
+    double *own = nullptr, *d = scal + SCAL_REDUCE;   // the usual case, a scalar or two: this slot of the device scalar block is the staging area
+    if (n > 8) { dev_alloc(own, n, Fill::None); d = own; }
     RX_HIP(hipMemcpyAsync(d, buf, sizeof(double) * n, hipMemcpyHostToDevice, stream));
     rccl_allreduce_dev(d, n);
     RX_HIP(hipMemcpyAsync(buf, d, sizeof(double) * n, hipMemcpyDeviceToHost, stream));
     sync_stream();
-    dev_free(d);
+    dev_free(own);
     return;
   }
   if (!has_comm || !comm.allreduce_sum) throw EngineError(RXMD_E_COMM, "vprocs > 1 needs a transport: call rxmd_hip_set_comm or rxmd_hip_comm_init_rccl first");
   if (comm.allreduce_sum(comm.ctx, buf, n)) throw EngineError(RXMD_E_COMM, "allreduce callback failed");
+}
+
+void Engine::allreduce_device(double *dev, int n, int h_stage, int site) {
+  Timed kt(this, &st.ms_allreduce, nullptr, &st.allreduce_calls, site);
+  if (nccl) { rccl_allreduce_dev(dev, n); return; }                // in stream order, no host round trip
+  if (!has_comm || !comm.allreduce_sum) throw EngineError(RXMD_E_COMM, "vprocs > 1 needs a transport: call rxmd_hip_set_comm or rxmd_hip_comm_init_rccl first");
+  double *h = h_scal + h_stage;                                    // a host transport (MPI callbacks): its all-reduce IS a host call
+  RX_HIP(hipMemcpyAsync(h, dev, sizeof(double) * n, hipMemcpyDeviceToHost, stream));
+  sync_stream();
+  if (comm.allreduce_sum(comm.ctx, h, n)) throw EngineError(RXMD_E_COMM, "allreduce callback failed");
+  RX_HIP(hipMemcpyAsync(dev, h, sizeof(double) * n, hipMemcpyHostToDevice, stream));
 }
 
 void Engine::collect_timers() {
@@ -590,12 +593,12 @@ __global__ void k_publish_words(int n, const int *__restrict__ src, unsigned lon
 }
 void Engine::build_ghosts_and_lists(bool qeq_prepass) {
   if (!atoms_set) throw EngineError(RXMD_E_STATE, "atoms were never set");
-  const KtPair t_lists = outer_begin(&st.ms_lists);   // (an event pair read at a later host wait: no wait of its own)
+  TimedSection t_lists(this, &st.ms_lists);           // (an event pair read at a later host wait: no wait of its own)
   bufs.refill(*this);                               // (RXMD_POISON_ALLOC only)
-  { const bool kt = kt_begin(&st.ms_ghost_build); ghost_build(); kt_end(kt); }
+  { Timed kt(this, &st.ms_ghost_build); ghost_build(); }
   bin_cells();
   build_prologue(3);
-  { const bool kt = kt_begin(&st.ms_k_blist); build_bonded_list(); kt_end(kt); }
+  { Timed kt(this, &st.ms_k_blist); build_bonded_list(); }
   sums_from_list = qeq_prepass;
   if (qeq_prepass) qeq_start_vectors();             // the sweep below also forms H.(qs,qt) of the CG start vector
   build_list10();
@@ -621,14 +624,12 @@ void Engine::build_ghosts_and_lists(bool qeq_prepass) {
     // The row stride of the 10 A list is sized from the MEAN density; a dense region inside a sparse box (a nanoparticle in
     // vacuum) can need more.  The reference stops (fixed MAXNEIGHBS10 = 1500, qeq.F90:248-252); here the list grows once to
     // what the sweep reported -- unless the caller fixed the stride (cfg.maxneighbs10), which keeps the reference's trap.
-    if (er.code != RXMD_E_MAXNEIGHBS10 || cfg.maxneighbs10 > 0) throw;
+    if (er.code != RXMD_E_MAXNEIGHBS10 || cfg.maxneighbs10 > 0) { collect_timers(); throw; }   // (the host has just waited: the pairs of a refused build go back to the pool)
     const int need = h_err[1];
     S10 = (static_cast<int>(need * 1.1) + 64 + 63) / 64 * 64;
     bufs.free_group(G_LIST10); bufs.alloc_group(*this, G_LIST10);   // (sized by rows10 * S10)
     st.n10_stride = S10;
-    list10_retry = true;
-    try { build_list10(); } catch (...) { list10_retry = false; throw; }
-    list10_retry = false;
+    { Restore<bool> retry(list10_retry, true); build_list10(); }
     check_device_error("list build");
   }
   nbonds = h_err[7]; nbonds_res = h_err[9];
@@ -638,7 +639,6 @@ void Engine::build_ghosts_and_lists(bool qeq_prepass) {
   lists_valid = true;
   if (!nb10_valid && !win_valid) require_nb10();       // the windows were lost in a build that counted on them: the row forms need the 4-byte entries (lists.hip: needs_nb10)
   collect_timers();
-  outer_end(t_lists);
   pq_matrix_stale = false;
 }
 

@@ -622,8 +622,7 @@ void Engine::halo_direct_exchange(double *v, int ncomp) {
 // a round are contiguous: one pack, one exchange, one unpack -- three rounds per halo when the stages pair, six otherwise.
 void Engine::halo_staged(double *v, int ncomp) {
   // QCOPY1 / QCOPY2 (comm.F90:2-100 with MODE_QCOPY*): on the second stream the part the main stream waits for is measured at the join
-  const bool kt = kt_begin(&st.ms_halo, in_comm_region ? nullptr : &st.ms_halo_exposed, &st.halo_calls, 1);
-  struct End { Engine *e; bool kt; ~End() { e->kt_end(kt); } } end_{this, kt};
+  Timed kt(this, &st.ms_halo, in_comm_region ? nullptr : &st.ms_halo_exposed, &st.halo_calls, 1);
   if (halo_direct && dh_ready) { halo_direct_exchange(v, ncomp); return; }
   const bool pairs = known_counts_pair();
   for (int i = 0; i < n_rounds(pairs); ++i) {

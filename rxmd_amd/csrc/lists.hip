@@ -633,12 +633,11 @@ void Engine::require_nb10() {
   // host took from the first sweep stay (h_err: the same numbers); the row sums of the CG start vector are not formed again (xs may have moved on)
   // The sweep takes atom index and type of a candidate from the w of the packed cell-sorted copy, where FORCE has put the charges since: the copy is
   // formed again first (the positions have not moved: the lists are valid) and gets its charges back behind the sweep.
-  const bool wv = win_valid, sfl = sums_from_list, retry = list10_retry, wq = sorted_w_charge;
+  const bool wv = win_valid, wq = sorted_w_charge;
   const int wg = win_groups;
   if (wq) sorted_positions();
-  sums_from_list = false; list10_retry = true;
-  try { build_list10(); } catch (...) { sums_from_list = sfl; list10_retry = retry; throw; }
-  sums_from_list = sfl; list10_retry = retry; win_valid = wv; win_groups = wg;
+  { Restore<bool> sums(sums_from_list, false), retry(list10_retry, true); build_list10(); }
+  win_valid = wv; win_groups = wg;
   if (wq) sorted_charge_only();
 }
 
@@ -661,12 +660,12 @@ void Engine::build_list10() {
   win_valid = false;
   build_windows();
   int *gflag = win_flag;
-  const bool kt10 = kt_begin(&st.ms_k_list10);
+  Timed kt10(this, &st.ms_k_list10);
   if (grid.ortho) k_win_columns<true><<<std::max(win_groups, 1), 32 * WIN_ROWS, 0, stream>>>(N, grid, cellid, cellstart, spos[0], spos[1], spos[2], dff.rctap_pad, rows_sorted, rowcols, grp_base, win_k, win_cnt, d_err);
   else k_win_columns<false><<<std::max(win_groups, 1), 32 * WIN_ROWS, 0, stream>>>(N, grid, cellid, cellstart, spos[0], spos[1], spos[2], dff.rctap_pad, rows_sorted, rowcols, grp_base, win_k, win_cnt, d_err);
   if (ff.pqeq) { if (selfcheck) RX_LIST10(true, true); else RX_LIST10(false, true); }
   else { if (selfcheck) RX_LIST10(true, false); else RX_LIST10(false, false); }
-  kt_end(kt10);
+  kt10.end();
 #undef RX_LIST10
 #undef RX_LIST10_O
 #undef RX_LIST10_F

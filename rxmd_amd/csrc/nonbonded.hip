@@ -110,7 +110,8 @@ __global__ void __launch_bounds__(64 * NB_WPB) k_nonbond(int N, int S10, DevFF f
     for (int k = 0; k < NB_WPB; ++k) s += sm[k][threadIdx.x];
     if (s != 0.0) atomicAdd(pe + 11 + threadIdx.x, s);
   }
-  if (threadIdx.x >= 64 && threadIdx.x < 70) {      // pe = scal + 32: the stress accumulators sit at scal + 48
+  static_assert(SCAL_ASTR == SCAL_PE + 16, "pe = scal + SCAL_PE: the stress accumulators astr are pe + 16");
+  if (threadIdx.x >= 64 && threadIdx.x < 70) {
     const int c = threadIdx.x - 64;
     double s = 0.0;
     for (int k = 0; k < NB_WPB; ++k) s += sv[k][c];
@@ -190,6 +191,7 @@ __global__ void __launch_bounds__(64 * WIN_ROWS, 8) k_nonbond_win(int N, int G, 
     for (int k = 0; k < WIN_ROWS; ++k) s += sm[k][threadIdx.x];
     if (s != 0.0) atomicAdd(pe + 11 + threadIdx.x, s);
   }
+  static_assert(SCAL_ASTR == SCAL_PE + 16, "pe = scal + SCAL_PE: the stress accumulators astr are pe + 16");
   if (threadIdx.x >= 64 && threadIdx.x < 70) {
     const int c = threadIdx.x - 64;
     double s = 0.0;
@@ -219,15 +221,15 @@ void Engine::nonbonded(bool to_fnb, bool energy) {
   const size_t lds = static_cast<size_t>(units) * WIN_UNIT * (sizeof(double4) + 1) + 16;
   if (win_valid && win_env && !list_selfcheck) {
 #define RX_NB_WIN(EN) k_nonbond_win<EN><<<win_groups, 64 * WIN_ROWS, lds, stream>>>(N, G, S10, dff, sl10, n10, rows_sorted, win_k, win_cnt, units, sorted_xyzi, sorted_type, pos[0], pos[1], pos[2], q, type, \
-                                                                 f0, f1, f2, scal + 32, assign)
+                                                                 f0, f1, f2, scal + SCAL_PE, assign)
     if (energy) RX_NB_WIN(true); else RX_NB_WIN(false);
 #undef RX_NB_WIN
     RX_HIP(hipGetLastError());
     return;
   }
   require_nb10();                                  // the row form reads the 4-byte entries
-  if (energy) k_nonbond<true><<<nblk(N, NB_WPB), 64 * NB_WPB, 0, stream>>>(N, S10, dff, nb10, n10, sorted_xyzi, pos[0], pos[1], pos[2], q, type, f0, f1, f2, scal + 32, assign);
-  else k_nonbond<false><<<nblk(N, NB_WPB), 64 * NB_WPB, 0, stream>>>(N, S10, dff, nb10, n10, sorted_xyzi, pos[0], pos[1], pos[2], q, type, f0, f1, f2, scal + 32, assign);
+  if (energy) k_nonbond<true><<<nblk(N, NB_WPB), 64 * NB_WPB, 0, stream>>>(N, S10, dff, nb10, n10, sorted_xyzi, pos[0], pos[1], pos[2], q, type, f0, f1, f2, scal + SCAL_PE, assign);
+  else k_nonbond<false><<<nblk(N, NB_WPB), 64 * NB_WPB, 0, stream>>>(N, S10, dff, nb10, n10, sorted_xyzi, pos[0], pos[1], pos[2], q, type, f0, f1, f2, scal + SCAL_PE, assign);
 }
 
 }  // namespace rxmd

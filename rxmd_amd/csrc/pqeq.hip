@@ -201,7 +201,8 @@ __global__ void __launch_bounds__(256) k_nonbond_pqeq(int N, int S10, DevFF ff, 
     for (int k = 0; k < 4; ++k) s += sm[k][threadIdx.x];
     if (s != 0.0) atomicAdd(pe + 11 + threadIdx.x, s);
   }
-  if (threadIdx.x >= 64 && threadIdx.x < 70) {      // pe = scal + 32: the stress accumulators sit at scal + 48
+  static_assert(SCAL_ASTR == SCAL_PE + 16, "pe = scal + SCAL_PE: the stress accumulators astr are pe + 16");
+  if (threadIdx.x >= 64 && threadIdx.x < 70) {
     const int c = threadIdx.x - 64;
     const double s = sv[0][c] + sv[1][c] + sv[2][c] + sv[3][c];
     if (s != 0.0) atomicAdd(pe + 16 + c, s);
@@ -221,7 +222,7 @@ void Engine::efield_force() {
 void Engine::nonbonded_pqeq() {
   require_nb10();
   k_nonbond_pqeq<<<nblk(N, 4), 256, 0, stream>>>(N, S10, dff, nb10, n10, sorted_xyzi, sorted_shl, pos[0], pos[1], pos[2], q, type, shl[0], shl[1], shl[2],
-                                                frc[0], frc[1], frc[2], scal + 32);
+                                                frc[0], frc[1], frc[2], scal + SCAL_PE);
 }
 
 }  // namespace rxmd

@@ -93,16 +93,16 @@ __device__ inline void scalar_algebra(int stage, double *__restrict__ scal, doub
       scal[S_STOP + par] = stop ? 1.0 : 0.0;      // two flags, by iteration parity: the kernels of iteration k read flag k & 1, which only update(k - 1) writes
       // a snapshot of the scalars of THIS iteration (parity par ^ 1) for the host: copied by a second stream while the main stream goes on with the
       // direction kernel; the slot is rewritten two iterations later, after the host has read it (run-ahead loop of Engine::qeq)
-      double *snap = scal + S_SNAP + 32 * (par ^ 1);
+      double *snap = scal + S_SNAP + S_SNAP_STRIDE * (par ^ 1);
       for (int c = 0; c < S_COUNT; ++c) snap[c] = scal[c];
       // run-ahead loop (round 6): the same snapshot straight into PINNED HOST memory, then its sequence number -- the host polls that word.  Until round 6
       // an event on the main stream, a wait + a 200-byte copy + an event on the second stream carried it: the event record alone cost the dependent
       // chain update -> direction ~7 us per iteration.
       if (hsnap != nullptr) {
-        double *hp = hsnap + 64 * (par ^ 1);
+        double *hp = hsnap + H_SNAP_STRIDE * (par ^ 1);
         for (int c = 0; c < S_COUNT; ++c) __hip_atomic_store(hp + c, scal[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");                  // system scope: the data before the sequence number
-        __hip_atomic_store(hp + 63, hseq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(hp + H_SNAP_SEQ, hseq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     }
   } else {
@@ -360,15 +360,8 @@ void Engine::qeq_start_vectors() {
 }
 
 void Engine::allreduce_scal4(int n) {
-  if (nprocs == 1 && !nccl) return;
-  const bool kt = kt_begin(&st.ms_allreduce, nullptr, &st.allreduce_calls, 0);
-  struct End { Engine *e; bool kt; ~End() { e->kt_end(kt); } } end_{this, kt};              // forced staged mode of a single rank without a communicator: nothing to add
-  if (nccl) { rccl_allreduce_dev(scal + S_RAW0, n); return; }      // in stream order, no host round trip
-  if (!has_comm || !comm.allreduce_sum) throw EngineError(RXMD_E_COMM, "vprocs > 1 needs a transport: call rxmd_hip_set_comm or rxmd_hip_comm_init_rccl first");
-  RX_HIP(hipMemcpyAsync(h_scal + 48, scal + S_RAW0, sizeof(double) * n, hipMemcpyDeviceToHost, stream));
-  sync_stream();
-  if (comm.allreduce_sum(comm.ctx, h_scal + 48, n)) throw EngineError(RXMD_E_COMM, "allreduce callback failed");
-  RX_HIP(hipMemcpyAsync(scal + S_RAW0, h_scal + 48, sizeof(double) * n, hipMemcpyHostToDevice, stream));
+  if (nprocs == 1 && !nccl) return;                                // forced staged mode of a single rank without a communicator: nothing to add
+  allreduce_device(scal + S_RAW0, n, H_SCAL_REDUCE, 0);            // (every CG iteration: sampled site 0)
 }
 
 // ---- the matrix pass: which instance, with which operands ---------------------------------------------------------------------------------------
@@ -642,7 +635,7 @@ void Engine::qeq() {
   if (!atoms_set) throw EngineError(RXMD_E_STATE, "atoms were never set");
   if (cfg.isQEq != 1 && cfg.isQEq != 2) { nstep_qeq = 0; return; }   // qeq.F90:60-61
   rows_live = false;
-  const KtPair t_qeq = outer_begin(&st.ms_qeq);
+  TimedSection t_qeq(this, &st.ms_qeq);
   // the list sweep of this step can form the row sums of the start vector on the way (saves the matrix pass of qeq.F90:87)
   const bool prepass_on = !opt.qeq_no_prepass;      // (experiments build only)
   sums_from_list = false;
@@ -664,9 +657,9 @@ void Engine::qeq() {
 }
 
 double Engine::qeq_start(const CgCall &c) {
-  RX_HIP(hipMemsetAsync(scal, 0, sizeof(double) * 32, stream));
-  h_scal[60] = cfg.QEq_tol;
-  RX_HIP(hipMemcpyAsync(scal + S_TOL, h_scal + 60, sizeof(double), hipMemcpyHostToDevice, stream));
+  RX_HIP(hipMemsetAsync(scal, 0, sizeof(double) * SCAL_CG_N, stream));
+  h_scal[H_SCAL_TOL] = cfg.QEq_tol;
+  RX_HIP(hipMemcpyAsync(scal + S_TOL, h_scal + H_SCAL_TOL, sizeof(double), hipMemcpyHostToDevice, stream));
   if (sums_from_list) {
     k_grad_start<<<c.vb, 256, 0, stream>>>(N, dff, type, qst, q, sall, sgh, gst, partials, pqrow);
     cg_reduce(3, c.vb);
@@ -718,9 +711,9 @@ int Engine::qeq_runahead(const CgCall &c, double &Est) {
     // sequence number last: nothing sits between the update and the direction kernel, and the host polls a word of its own memory
     snap_expect[k & 1] = static_cast<double>(++snap_seq);
     if (roword) k_cg_update<true><<<c.vb_upd, 256, 0, stream>>>(R, dff, scal, r_type, r_hst, r_qst, r_wall, r_wgh, r_sall, r_sgh, r_gst, partials, tickets + 1, pqrow, 6 | (((k + 1) & 1) << 4), stopflag,
-                                                                  h_scal + 64, snap_expect[k & 1], rows_sorted, N);
+                                                                  h_scal + H_SCAL_SNAP, snap_expect[k & 1], rows_sorted, N);
     else k_cg_update<true><<<c.vb_upd, 256, 0, stream>>>(N, dff, scal, type, hst, qst, wall, wgh, sall, sgh, gst, partials, tickets + 1, pqrow, 6 | (((k + 1) & 1) << 4), stopflag,
-                                                           h_scal + 64, snap_expect[k & 1]);
+                                                           h_scal + H_SCAL_SNAP, snap_expect[k & 1]);
     const bool scatter = c.cg_scatter && k + 1 <= nmax - 1;
     if (roword) { k_cg_direction<false><<<c.vb, 256, 0, stream>>>(R, dff, scal, r_type, r_gst, r_hst, r_hst2, r_qst, r_sall, r_sgh, q, partials, tickets + 2, pqrow, -1, G, invpos, g_rrow, scatter ? xs : nullptr, stopflag,
                                                                     rows_sorted, N, r_xpos); std::swap(r_hst, r_hst2); }
@@ -742,7 +735,7 @@ int Engine::qeq_runahead(const CgCall &c, double &Est) {
     wait_snapshot((it - 1) & 1, snap_expect[(it - 1) & 1]);     // iteration it - 1 has produced its Est and the decision about iteration it
     if (it == 1) est_trace[0] = h_scal[S_EST];      // (the start vector's Est: copied before anything of iteration 0 ran)
     collect_timers();
-    const double *hs = h_scal + 64 + 64 * ((it - 1) & 1);
+    const double *hs = h_scal + H_SCAL_SNAP + H_SNAP_STRIDE * ((it - 1) & 1);
     Est = hs[S_EST];
     est_trace.push_back(Est);
     if (pass_timed_k[(it - 1) & 1]) { float pms = 0; if (hipEventElapsedTime(&pms, ev_pass[(it - 1) & 1][0], ev_pass[(it - 1) & 1][1]) == hipSuccess) { pass_timed_ms += pms; pass_timed_n += 1; } }
@@ -855,13 +848,13 @@ int Engine::qeq_host_paced(const CgCall &c, double &Est) {
   return it;
 }
 
-void Engine::qeq_finish(int it, double Est, KtPair t_qeq) {
+void Engine::qeq_finish(int it, double Est, TimedSection &t_qeq) {
   if (ff.pqeq) pqeq_update_shells();                  // pqeq.F90:169
   nstep_qeq = it; last_est = Est;
   st.qeq_iters_last = it; st.qeq_iters_total += it; st.qeq_calls += 1; qeq_iters_smooth = qeq_iters_smooth < 0.0 ? it : 0.75 * qeq_iters_smooth + 0.25 * it;
   // No host wait here (round 5): after a run-ahead loop the kernels of the iteration that did not happen are still in the queue (they return at once and store
   // no snapshot) and FORCE queues behind them in stream order.  (Until round 5 a sync here cost ~50 us of idle GPU per step.)
-  outer_end(t_qeq);
+  t_qeq.end();
   if (!place_tuned && win_used && it >= 1 && qeq_bits_req != 32) { sync_stream(); collect_timers(); tune_window_placement(); }
 }
 

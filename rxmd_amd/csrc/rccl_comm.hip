@@ -89,7 +89,7 @@ void Engine::sync_event(hipEvent_t ev_) {
 // last (qeq.hip: scalar_algebra stage 6); the host polls that word -- no HIP call on the way.  Bounded: beyond 2 ms (twice a matrix pass) every round
 // asks the stream whether the device is still alive, yields the core, and gives up after the time limit of every other wait.
 void Engine::wait_snapshot(int parity, double seq) {
-  volatile const double *flag = h_scal + 64 + 64 * parity + 63;
+  volatile const double *flag = h_scal + H_SCAL_SNAP + H_SNAP_STRIDE * parity + H_SNAP_SEQ;
   const auto t0 = std::chrono::steady_clock::now();
   unsigned spins = 0;
   for (;;) {

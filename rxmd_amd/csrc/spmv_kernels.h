@@ -11,9 +11,7 @@ namespace rxmd {
 
 static inline int nblk(long long n, int b) { return n > 0 ? static_cast<int>((n + b - 1) / b) : 1; }   // an empty rank still launches (kernels guard their range)
 
-enum { S_MU = 0, S_LMIN_S, S_LMIN_T, S_GOLD_S, S_GOLD_T, S_GNEW_S, S_GNEW_T, S_EST, S_GH_S, S_GH_T, S_HSH_S, S_HSH_T, S_SSUM, S_TSUM, S_BETA_S, S_BETA_T, S_RAW0, S_RAW1, S_RAW2, S_RAW3, S_RAW4, S_RAW5, S_RAW6, S_RAW7, S_STOP, S_STOP1, S_TOL, S_COUNT };
-enum { MODE_HSH = 0, MODE_GRAD = 1 };
-constexpr int S_SNAP = 128;      // scal[S_SNAP + 32 p ..]: snapshot of the scalars of an iteration of parity p (scalar_algebra stage 6)
+enum { MODE_HSH = 0, MODE_GRAD = 1 };      // (the CG scalars S_* and their snapshot slots: the layout block of engine.h)
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 #ifndef SPMV_UNR
 #define SPMV_UNR 4

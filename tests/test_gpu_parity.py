@@ -1107,6 +1107,52 @@ def test_row_stride_of_the_10A_list_grows_when_the_density_estimate_is_too_low()
     e.close()
 
 
+def test_refused_calls_hand_their_timer_pairs_back():
+    """The ms_* timers draw event pairs from a pool of 64.  A refused QEq() -- the fixed 10 A stride of the test above -- holds two section pairs
+    (the QEq call, the list build) when the error unwinds; 40 refusals would take 80 pairs from a pool that lost them."""
+    import rxmd_amd
+    from rxmd_amd import system
+    ff, names, frac, lat = oa.make_system("sicnp")
+    lat3, rec = system.geninit(ff, names, frac, lat, mc=(1, 1, 1))
+    e = rxmd_amd.RxmdEngine(ff, lat3, maxneighbs10=64)
+    e.set_atoms_rxff(rec)
+    for k in range(40):
+        with pytest.raises(rxmd_amd.RxmdError) as ex:
+            e.QEq()
+        assert ex.value.code == -5, (k, str(ex.value))
+    dropped = e.stats()["timer_pairs_dropped"]
+    print("timer_pairs_dropped after 40 refused QEq calls: %d" % dropped)
+    assert dropped == 0
+    e.close()
+
+
+def test_kernel_timers_still_run_after_a_refusal_inside_a_timed_region():
+    """The ghost build runs inside a kernel timer; a capacity refusal there (NBUFFER = 1000 against 168 RDX atoms and their images, as in
+    test_error_codes_mirror_reference_traps) must not leave that timer open: an open one keeps every later kernel timer from starting.
+    The valid call behind the refusals: the first 21 atoms alone, at most 26 images each, fit the same 1000 slots."""
+    import rxmd_amd
+    from rxmd_amd import system
+    ff, names, frac, lat = oa.make_system("rdx168")
+    lat3, rec = system.geninit(ff, names, frac, lat)
+    e = rxmd_amd.RxmdEngine(ff, lat3, nbuffer=1000)
+    e.set_atoms_rxff(rec)
+    for k in range(3):
+        with pytest.raises(rxmd_amd.RxmdError) as ex:
+            e.FORCE()
+        assert ex.value.code == -3, (k, str(ex.value))
+    e.set_atoms_rxff(rec[:21])
+    e.reset_timers()
+    e.QEq()
+    pe = e.FORCE()
+    assert np.isfinite(pe).all()
+    st = e.stats()
+    timed = {k: st[k] for k in ("ms_ghost_build", "ms_k_blist", "ms_k_list10", "ms_k_bondorder", "ms_k_nonbond", "ms_k_e3b", "ms_k_e4b", "ms_k_assemble")}
+    print("kernel timers of the valid call behind three refusals:", timed, "dropped", st["timer_pairs_dropped"])
+    assert all(v > 0.0 for v in timed.values()), timed
+    assert st["timer_pairs_dropped"] == 0
+    e.close()
+
+
 def test_forces_and_charges_are_bitwise_reproducible_run_to_run():
     """no result may depend on scheduling: partial sums are combined in fixed orders, the torsion accumulators use LDS atomics whose
     order is fixed by queue and lane order; only the 14 energy scalars and the hydrogen-bond acceptor forces take global atomics.
