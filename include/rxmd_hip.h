@@ -199,6 +199,30 @@ int rxmd_hip_get_lex(rxmd_handle h, int natoms, double *qsfp, double *qsfv);
 int rxmd_hip_evaluate_device(rxmd_handle h, int natoms, const long long *gid, const int *type, const double *pos3, const double *q_in,
                              double *f3, double *q_out, double pe[14], double virial6[6], void *stream);
 
+/* The bond-order graph of the last FORCE as coordinate (COO) arrays in DEVICE memory: the residents' bond lists -- what rxmd_hip_get_bonds copies
+ * to the host as padded [natoms][32] arrays -- compacted on the device.  Every entry of a resident's list with BO(0) >= bo_min is selected
+ * (bo_min <= 0: all), in resident order and list order within the atom: the row-major walk of rxmd_hip_get_bonds.  The graph is DIRECTED: a bond
+ * between two residents appears once from each end.  The compaction is a scan: stable, the same order on every call.
+ *   src[e]      local index of the owning resident (the order of rxmd_hip_get_atoms, and the caller's order after rxmd_hip_evaluate_device)
+ *   dst[e]      local index of the resident that owns the partner (a ghost partner is resolved to its owner); single rank only
+ *               with RXMD_BONDS_GID in flags both are global ids instead (any vprocs: a remote partner's id travels with its ghost)
+ *   bo[e]       BO(0), the corrected total bond order: the double rxmd_hip_get_bonds returns
+ *   bo3[3e..]   BO(1), BO(2), BO(3) = sigma, pi, double-pi after the corrections (bo.F90:207-215: BO(1) = BO(0) - BO(2) - BO(3)); NULL: not wanted
+ *   vec3[3e..]  r_partner - r_owner with the partner's coordinates as the engine holds them: a ghost already is the right periodic image, so this is
+ *               the bond vector itself in any cell, triclinic included, and it does not depend on where in space the caller's positions were; NULL: not wanted
+ * All five are device pointers.  Returns E, the number of directed bonds selected, or a negative RXMD_E_* code.  src = dst = bo = NULL: count only
+ * (capacity, bo3, vec3 ignored).  Otherwise src, dst and bo go together (RXMD_E_ARG when one is missing) and hold `capacity` entries (bo3, vec3:
+ * 3 * capacity doubles); when capacity < E NOTHING is written and E is still returned, so the caller compares.  One host wait per call, for E.
+ * The engine works on its own stream: `stream` (NULL = the null stream), on which the caller consumes the arrays, is made to wait for an event
+ * recorded behind the fill kernel, and the fill kernel waits for what `stream` held at entry.
+ * RXMD_E_STATE: no FORCE yet, or set_atoms / set_lattice / set_charges since the last one (the rule of rxmd_hip_get_bonds).  After rxmd_hip_step the
+ * tables and positions are those of the last step's FORCE.  Engines created with pqeq_path are fine.  RXMD_E_ARG (checked first): unknown bits in
+ * flags, capacity < 0, a non-finite bo_min, local indices (no RXMD_BONDS_GID) on an engine with vprocs other than 1 1 1.
+ * The arrays are plain numbers: no gradient flows through them.  No counterpart in the reference (WriteBND walks nbrlist on the host). */
+#define RXMD_BONDS_GID 1   /* src/dst are global ids instead of local resident indices */
+long long rxmd_hip_get_bonds_device(rxmd_handle h, int flags, double bo_min, long long capacity, long long *src, long long *dst, double *bo,
+                                    double *bo3, double *vec3, void *stream);
+
 /* ---- introspection for tests, roofline accounting and the timers table (main.F90:135-182) ---- */
 typedef struct rxmd_stats {
   int natoms, nghost_qeq, nghost_force; /* copyptr(6)-NATOMS after the QEq / FORCE ghost builds */

@@ -188,6 +188,8 @@ void Engine::declare_buffers() {
   b.add(xbuf_send, G_XBUF, Dim::Cap, 1, 0, P, whole);         // (host-supplied exchange buffers carry no record: never refilled, never freed)
   b.add(xbuf_recv, G_XBUF, Dim::Cap, 1, 0, P, whole);
   b.add(dh_serve, G_DH_SERVE, Dim::Cap, 1, 0, P, never);
+  b.add(bg_flag, G_BGRAPH, Dim::Cap, 1, 1, P, never);         // rxmd_hip_get_bonds_device (device_io.hip): selection flag and output offset per entry of the
+  b.add(bg_off, G_BGRAPH, Dim::Cap, 1, 1, P, never);          // bond tables, capacity = bcap of the day of the call; an engine that never asks has neither
 }
 
 size_t Buffers::count(const Buf &b, const Engine &e) const {

@@ -413,6 +413,13 @@ int rxmd_hip_evaluate_device(rxmd_handle h, int natoms, const long long *gid, co
   return guarded(h, [&](Engine &e) { e.evaluate_device(natoms, gid, type, pos3, q_in, f3, q_out, pe, virial6, static_cast<hipStream_t>(stream)); });
 }
 
+long long rxmd_hip_get_bonds_device(rxmd_handle h, int flags, double bo_min, long long capacity, long long *src, long long *dst, double *bo,
+                                    double *bo3, double *vec3, void *stream) {
+  long long n = 0;
+  const int rc = guarded(h, [&](Engine &e) { n = e.bonds_device(flags, bo_min, capacity, src, dst, bo, bo3, vec3, static_cast<hipStream_t>(stream)); });
+  return rc < 0 ? rc : n;
+}
+
 // ---- introspection ----
 int rxmd_hip_get_stats(rxmd_handle h, rxmd_stats *out) {
   if (!out) return RXMD_E_ARG;

@@ -5,7 +5,11 @@
 //                     extended-Lagrangian state zeroed; the start charges; a type outside the ffield raises the device error word
 //   k_egress_device   frc[a] -> f3[natoms][3], q -> q_out, and the six virial sums this FORCE call added to the stress accumulators
 // Single rank only: the atoms keep the caller's order because nothing migrates between ingest and egress.
+// rxmd_hip_get_bonds_device, at the end of the file, is the way OUT for the bond-order graph FORCE leaves in the compact bond tables: two more kernels
+//   k_bond_select / k_bond_fill   flag per table entry, exclusive sum, coordinate arrays (src, dst, bo, the three parts of bo, the bond vector)
 #include "engine.h"
+
+#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -140,6 +144,82 @@ void Engine::evaluate_device(int natoms, const long long *gid_d, const int *type
   if (pe_out) for (int k = 0; k < 14; ++k) pe_out[k] = pe[k];
   if (virial_out) for (int c = 0; c < 6; ++c) virial_out[c] = h_scal[H_SCAL_EVAL_VIRIAL + c];
   eval_natoms = natoms;
+}
+
+// ---- rxmd_hip_get_bonds_device: the bond-order graph as coordinate arrays ---------------------------------------------------------------
+// A lane per entry o of the residents' part of the compact tables (o < boff[N] = nbonds_res), three launches:
+//   k_bond_select   flag[o] = bo0[o] >= bo_min (bo_min <= 0: every entry); flag[n] = 0 so that the exclusive sum behind it leaves the total in off[n]
+//   hipcub exclusive sum flag -> off: a stable compaction in table order (resident order, then list order), no atomics
+//   k_bond_fill     entry o -> output e = off[o].  bown / nbr / bo0..3 / flag / off are read coalesced and the outputs stored coalesced where the selection
+//                   is dense; gid / groot / pos are gathers by atom index.  Per selected entry: 4 + 4 + 4 + 4 bytes of indices and 8 of bo0 in, 24 out
+//                   (src, dst, bo); + 24 in and 24 out for bo3; + 48 gathered and 24 out for vec3; + 16 gathered for global ids or 4 for a ghost's root.
+// Nothing here is on the path of qeq(), force() or step().
+__global__ void __launch_bounds__(256) k_bond_select(int n, double bo_min, const double *__restrict__ bo0, int *__restrict__ flag) {
+  const int o = blockIdx.x * blockDim.x + threadIdx.x;
+  if (o > n) return;
+  flag[o] = (o < n && (bo_min <= 0.0 || bo0[o] >= bo_min)) ? 1 : 0;
+}
+
+// The owner of a ghost partner: groot[j] where the self exchange filled it (the 26-segment build and the local staged build, exchange.hip), or the owner's
+// local index the staged exchange carries with every atom (gowner = index * 1024 + rank, k_pack_ghosts) when one rank runs through the transport.
+__global__ void __launch_bounds__(256) k_bond_fill(int n, int nres, int as_gid, const int *__restrict__ flag, const int *__restrict__ off,
+                                                    const int *__restrict__ bown, const int *__restrict__ nbr, const double *__restrict__ bo0,
+                                                    const double *__restrict__ bo1, const double *__restrict__ bo2, const double *__restrict__ bo3,
+                                                    const long long *__restrict__ gid, const int *__restrict__ groot, const long long *__restrict__ gowner,
+                                                    const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
+                                                    long long *__restrict__ src, long long *__restrict__ dst, double *__restrict__ bo,
+                                                    double *__restrict__ parts3, double *__restrict__ vec3) {
+  const int o = blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= n || !flag[o]) return;
+  const size_t e = static_cast<size_t>(off[o]);
+  const int i = bown[o], j = nbr[o];
+  if (as_gid) { src[e] = gid[i]; dst[e] = gid[j]; }
+  else {
+    src[e] = i;
+    dst[e] = j < nres ? j : (gowner ? static_cast<int>(gowner[j] >> 10) : groot[j]);
+  }
+  bo[e] = bo0[o];
+  if (parts3) { parts3[3 * e] = bo1[o]; parts3[3 * e + 1] = bo2[o]; parts3[3 * e + 2] = bo3[o]; }
+  if (vec3) { vec3[3 * e] = x[j] - x[i]; vec3[3 * e + 1] = y[j] - y[i]; vec3[3 * e + 2] = z[j] - z[i]; }   // the ghost IS the right periodic image: no minimum-image step
+}
+
+long long Engine::bonds_device(int flags, double bo_min, long long capacity, long long *src_d, long long *dst_d, double *bo_d, double *bo3_d, double *vec3_d, hipStream_t user) {
+  const bool count_only = !src_d && !dst_d && !bo_d;
+  const bool as_gid = (flags & RXMD_BONDS_GID) != 0;
+  if (flags & ~RXMD_BONDS_GID) throw EngineError(RXMD_E_ARG, "get_bonds_device: unknown bit in flags");
+  if (!std::isfinite(bo_min)) throw EngineError(RXMD_E_ARG, "get_bonds_device: bo_min must be finite");
+  if (!count_only && (!src_d || !dst_d || !bo_d)) throw EngineError(RXMD_E_ARG, "get_bonds_device: src, dst and bo go together (all three NULL: count only)");
+  if (!count_only && capacity < 0) throw EngineError(RXMD_E_ARG, "get_bonds_device: negative capacity");
+  if (!as_gid && nprocs != 1) throw EngineError(RXMD_E_ARG, "get_bonds_device: local indices need a single rank (vprocs 1 1 1); ask for global ids (RXMD_BONDS_GID)");
+  if (!atoms_set || !lists_valid) throw EngineError(RXMD_E_STATE, "no bond lists: call rxmd_hip_force first");
+  if (force_pending) finish_force();               // (FORCE itself joins the bonded chain's stream and the halo stream in front of its end)
+  const int n = nbonds_res;
+  if (n <= 0) return 0;
+  if (!bg_flag || bufs.cap[G_BGRAPH] < bcap) {       // first use, or the bond tables have grown since
+    sync_stream();                                   // (the fill kernel of an earlier call may still read the old blocks)
+    bufs.free_group(G_BGRAPH); bufs.alloc_group(*this, G_BGRAPH, bcap);
+  }
+  size_t need = 0;
+  RX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, bg_flag, bg_off, n + 1, stream));
+  if (need > cubtmp_bytes) {                         // (sized at set-up for NB + 1 items; a dense box has more bonds than atom slots)
+    sync_stream();
+    bufs.free_group(G_CUBTMP); cubtmp_bytes = need + 256; bufs.alloc_group(*this, G_CUBTMP, cubtmp_bytes);
+  }
+  k_bond_select<<<nblk(static_cast<long long>(n) + 1, 256), 256, 0, stream>>>(n, bo_min, bo0, bg_flag);
+  size_t tb = cubtmp_bytes;
+  RX_HIP(hipcub::DeviceScan::ExclusiveSum(cubtmp, tb, bg_flag, bg_off, n + 1, stream));
+  RX_HIP(hipMemcpyAsync(h_cnt + 2, bg_off + n, sizeof(int), hipMemcpyDeviceToHost, stream));
+  sync_stream();                                     // the host wait of the call
+  const long long E = h_cnt[2];
+  if (count_only || capacity < E || E == 0) return E;
+  if (!ev_io_in) { RX_HIP(hipEventCreateWithFlags(&ev_io_in, hipEventDisableTiming)); RX_HIP(hipEventCreateWithFlags(&ev_io_out, hipEventDisableTiming)); }
+  RX_HIP(hipEventRecord(ev_io_in, user));            // whatever the caller's stream still does with the output arrays comes first
+  RX_HIP(hipStreamWaitEvent(stream, ev_io_in, 0));
+  k_bond_fill<<<nblk(n, 256), 256, 0, stream>>>(n, N, as_gid ? 1 : 0, bg_flag, bg_off, bown, nbr, bo0, bo1, bo2, bo3, gid, groot, multi() ? gowner : nullptr,
+                                                pos[0], pos[1], pos[2], src_d, dst_d, bo_d, bo3_d, vec3_d);
+  RX_HIP(hipEventRecord(ev_io_out, stream));
+  RX_HIP(hipStreamWaitEvent(user, ev_io_out, 0));
+  return E;
 }
 
 }  // namespace rxmd

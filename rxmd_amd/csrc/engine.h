@@ -189,7 +189,7 @@ enum class Dim : unsigned char { Fixed, NB, Rows10, List10, Cap };   // what a b
 enum class Refill : unsigned char { Never, Whole, Ghosts };          // RXMD_POISON_ALLOC refill before a rebuild: none, the whole buffer, elements [N, NB)
 enum class Space : unsigned char { Device, Pinned, PinnedCoherent };
 // re-allocation groups.  Those before G_ON_DEMAND exist from set-up on (Buffers::alloc_setup); the others are allocated when first needed
-enum { G_SETUP, G_BOND, G_WIN, G_CELLSTART, G_LIST10, G_PARTIALS, G_ON_DEMAND, G_CUBTMP = G_ON_DEMAND, G_FFBLOB, G_PQBLOB, G_E4B, G_SEG, G_SEG_PINNED, G_XBUF, G_DH_SERVE, G_COUNT };
+enum { G_SETUP, G_BOND, G_WIN, G_CELLSTART, G_LIST10, G_PARTIALS, G_ON_DEMAND, G_CUBTMP = G_ON_DEMAND, G_FFBLOB, G_PQBLOB, G_E4B, G_SEG, G_SEG_PINNED, G_XBUF, G_DH_SERVE, G_BGRAPH, G_COUNT };
 enum : unsigned { BUF_PQEQ = 1u, BUF_RESIDENT = 2u, BUF_QEQ_F32 = 4u };   // exists only with PQEq ; resident state that grow_capacity carries over ; exists only while the fp32 matrix stream is requested (set_qeq_precision)
 struct Buf { void **pp; size_t elem; int group; Dim dim; size_t mul, add_; Fill fill; Refill refill; unsigned flags; Space space; size_t bytes; };   // bytes: what was allocated (0: nothing of ours)
 struct Buffers {
@@ -373,6 +373,11 @@ struct Engine {
   void size_from_device_arrays(int natoms, const int *type_d, const double *pos3_d, hipStream_t user);
   hipEvent_t ev_io_in = nullptr, ev_io_out = nullptr;
   int eval_natoms = -1;
+  // rxmd_hip_get_bonds_device (device_io.hip): the residents' part of the compact bond tables as coordinate (COO) arrays in DEVICE memory, entries with
+  // bo0 >= bo_min in table order -- flag per entry, exclusive sum, fill.  src = dst = bo = nullptr: count only.  Returns the number selected; nothing is
+  // written when capacity is smaller.  bg_flag / bg_off: its scratch, one int per table entry + 1, allocated on first use at the capacity of the bond tables
+  long long bonds_device(int flags, double bo_min, long long capacity, long long *src_d, long long *dst_d, double *bo_d, double *bo3_d, double *vec3_d, hipStream_t user);
+  int *bg_flag = nullptr, *bg_off = nullptr;
   void build_ghosts_and_lists(bool qeq_prepass = false);   // COPYATOMS(MODE_COPY) + LINKEDLIST + NEIGHBORLIST + 10 A list/hessian, once per step
   void qeq_start_vectors();        // qs, qt, hs, ht of qeq.F90:36-63 and their cell-sorted copy (before the list sweep that uses them)
   int *rows_int = nullptr, *rows_bnd = nullptr; int n_bnd = 0; bool rows_split_pending = false;   // interior / boundary rows (multi-rank)

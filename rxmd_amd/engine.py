@@ -13,6 +13,7 @@ from . import _lib
 from ._lib import RxmdConfig, RxmdStats
 
 PE_NAMES = ["Esystem", "Ebond", "Elp", "Eover", "Eunder", "Eval", "Epen", "Ecoa", "Etors", "Econj", "Ehbond", "Evdwaals", "Ecoulomb", "Echarge"]
+BONDS_GID = 1      # RXMD_BONDS_GID of include/rxmd_hip.h
 
 
 class RxmdError(RuntimeError):
@@ -249,6 +250,16 @@ class RxmdEngine:
         p = [C.c_void_p(int(a) or None) for a in (gid_ptr, type_ptr, pos_ptr, q_in_ptr, f_ptr, q_out_ptr)]
         self._chk(self.L.rxmd_hip_evaluate_device(self.h, int(natoms), p[0], p[1], p[2], p[3], p[4], p[5], _ptr(pe), _ptr(vir), C.c_void_p(int(stream) or None)))
         return pe, vir
+
+    def bonds_device(self, capacity, src_ptr, dst_ptr, bo_ptr, bo3_ptr=0, vec_ptr=0, bo_min=0.0, as_gid=False, stream=0):
+        """the bond-order graph of the last FORCE as coordinate arrays in device memory, given as integer addresses (include/rxmd_hip.h:
+        rxmd_hip_get_bonds_device): int64 src[capacity], dst[capacity], float64 bo[capacity], optional float64 bo3[capacity][3] (sigma, pi,
+        double-pi) and vec[capacity][3] (r_dst - r_src, the right periodic image).  Every list entry with bo >= bo_min, in the row-major order of
+        bonds(); directed.  src / dst are local indices (the order of atoms()), global ids with as_gid.  src_ptr = dst_ptr = bo_ptr = 0: count only.
+        -> E, the number of directed bonds selected; nothing is written when capacity < E"""
+        p = [C.c_void_p(int(a) or None) for a in (src_ptr, dst_ptr, bo_ptr, bo3_ptr, vec_ptr)]
+        return self._chk(self.L.rxmd_hip_get_bonds_device(self.h, BONDS_GID if as_gid else 0, float(bo_min), int(capacity), p[0], p[1], p[2], p[3], p[4],
+                                                          C.c_void_p(int(stream) or None)))
 
     # ---- introspection ----
     def stats(self):

@@ -8,6 +8,10 @@ a bias potential, an integrator or a correction model written in torch composes 
     model = ReaxFF(ffield, lattice, types)
     out = model.evaluate(pos)           # dict(energy, forces, charges, pe, virial)
     e = model(pos); e.backward()        # pos.grad == -forces
+    g = model.bond_graph(bo_min=0.3)    # dict(edge_index [2, E], bond_order [E], edge_vec [E, 3]) of the last evaluate, device tensors
+
+The bond-order graph (`bond_graph`, or `evaluate(pos, bond_graph=bo_min)`) is what FORCE left in the engine's bond tables, compacted on the device
+(RxmdEngine.bonds_device -> rxmd_hip_get_bonds_device).  It is NOT differentiable: bond orders and bond vectors come out as constants.
 
 Single rank, plain QEq (isQEq 0 or 1).  No second derivatives, no gradient with respect to the lattice.
 This module imports torch; `import rxmd_amd` does not import it.
@@ -17,6 +21,13 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from .engine import RxmdEngine
+
+
+def _check_bo_min(bo_min):
+    """ValueError unless bo_min is a real number (a bool is not); touches no GPU"""
+    if isinstance(bo_min, (bool, np.bool_)) or not isinstance(bo_min, (int, float, np.integer, np.floating)):
+        raise ValueError("bo_min must be a real number, got %s" % type(bo_min).__name__)
+    return float(bo_min)
 
 
 def _check_pos(pos, natoms, device):
@@ -64,10 +75,13 @@ class ReaxFF:
             raise ValueError("types must be one-dimensional and not empty, and gid must match it")
         self.types, self.gid, self.natoms = types, gid, int(types.shape[0])
 
-    def evaluate(self, pos, q0=None):
+    def evaluate(self, pos, q0=None, bond_graph=None):
         """QEq + FORCE at pos [N, 3] (float64, CUDA, anywhere in space; not modified).  q0: start charges [N] (isQEq = 0: the charges used); None:
-        the previous call's solution.  -> energy (0-dim device tensor), forces [N, 3], charges [N] (fresh device tensors), pe[14], virial[6] (CPU)"""
+        the previous call's solution.  -> energy (0-dim device tensor), forces [N, 3], charges [N] (fresh device tensors), pe[14], virial[6] (CPU).
+        bond_graph = <number>: also "bonds" = self.bond_graph(bo_min=<number>), the bond-order graph of this call (constants: not differentiable)"""
         _check_pos(pos, self.natoms, self.device)
+        if bond_graph is not None:
+            bond_graph = _check_bo_min(bond_graph)
         if q0 is not None:
             if not isinstance(q0, torch.Tensor) or q0.dtype != torch.float64 or q0.shape != (self.natoms,) or q0.device != self.device:
                 raise ValueError("q0 must be a float64 CUDA tensor of shape [%d] on %s" % (self.natoms, self.device))
@@ -80,7 +94,44 @@ class ReaxFF:
             pe, vir = self.engine.evaluate_device(self.natoms, self.types.data_ptr(), p.data_ptr(), forces.data_ptr(), charges.data_ptr(),
                                                   gid_ptr=0 if self.gid is None else self.gid.data_ptr(), q_in_ptr=0 if q0 is None else q0.data_ptr(), stream=stream)
             energy = torch.tensor(pe[0], dtype=torch.float64, device=self.device)
-        return dict(energy=energy, forces=forces, charges=charges, pe=torch.from_numpy(pe), virial=torch.from_numpy(vir))
+        out = dict(energy=energy, forces=forces, charges=charges, pe=torch.from_numpy(pe), virial=torch.from_numpy(vir))
+        if bond_graph is not None:
+            out["bonds"] = self.bond_graph(bo_min=bond_graph)
+        return out
+
+    def bond_graph(self, bo_min=0.0, components=False):
+        """The bond-order graph of the last evaluate / energy call (RxmdError -7 before the first, or after set_lattice), as fresh tensors on the
+        model's device, produced on torch's current stream:
+            edge_index [2, E] int64    (src, dst) in the caller's atom order; directed: a bond appears once from each end (`src < dst` keeps one)
+            bond_order [E]    float64  the corrected total bond order BO(0); every entry of the engine's bond lists with bond_order >= bo_min
+            edge_vec   [E, 3] float64  r_dst - r_src through the right periodic image: the bond vector itself, wherever in space pos was given
+            bond_order_parts [E, 3]    with components=True: sigma, pi, double-pi (they sum to bond_order)
+        Edges are ordered by src, then by the engine's list order.  Count, allocate exactly, fill: two short device passes, one host wait each.
+
+        NOT differentiable: these are constants, no gradient reaches pos through them.  For differentiable bond lengths recover the integer image
+        shift once and recompute in torch (H = the lattice vectors as columns):
+            src, dst = g["edge_index"]
+            shift = torch.round((g["edge_vec"] - (pos[dst] - pos[src])) @ torch.linalg.inv(H).T)       # [E, 3] integers, constants
+            d = (pos[dst] - pos[src] + shift @ H.T).norm(dim=1)                                       # differentiable in pos"""
+        bo_min = _check_bo_min(bo_min)
+        if not isinstance(components, (bool, np.bool_)):
+            raise ValueError("components must be a bool, got %s" % type(components).__name__)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            E = self.engine.bonds_device(0, 0, 0, 0, bo_min=bo_min, stream=stream)
+            kw = dict(device=self.device)
+            edge = torch.empty((2, E), dtype=torch.int64, **kw)
+            bo = torch.empty(E, dtype=torch.float64, **kw)
+            vec = torch.empty((E, 3), dtype=torch.float64, **kw)
+            parts = torch.empty((E, 3), dtype=torch.float64, **kw) if components else None
+            if E > 0:
+                got = self.engine.bonds_device(E, edge[0].data_ptr(), edge[1].data_ptr(), bo.data_ptr(), bo3_ptr=parts.data_ptr() if components else 0,
+                                               vec_ptr=vec.data_ptr(), bo_min=bo_min, stream=stream)
+                assert got == E, "the bond tables changed between the count and the fill"
+        out = dict(edge_index=edge, bond_order=bo, edge_vec=vec)
+        if components:
+            out["bond_order_parts"] = parts
+        return out
 
     def energy(self, pos):
         """potential energy as a differentiable function of pos: d energy / d pos = -forces (first derivatives only)"""
