@@ -218,10 +218,30 @@ int rxmd_hip_evaluate_device(rxmd_handle h, int natoms, const long long *gid, co
  * RXMD_E_STATE: no FORCE yet, or set_atoms / set_lattice / set_charges since the last one (the rule of rxmd_hip_get_bonds).  After rxmd_hip_step the
  * tables and positions are those of the last step's FORCE.  Engines created with pqeq_path are fine.  RXMD_E_ARG (checked first): unknown bits in
  * flags, capacity < 0, a non-finite bo_min, local indices (no RXMD_BONDS_GID) on an engine with vprocs other than 1 1 1.
- * The arrays are plain numbers: no gradient flows through them.  No counterpart in the reference (WriteBND walks nbrlist on the host). */
+ * The arrays are plain numbers; their derivative with respect to the positions is rxmd_hip_bonds_vjp_device below.  No counterpart in the
+ * reference (WriteBND walks nbrlist on the host). */
 #define RXMD_BONDS_GID 1   /* src/dst are global ids instead of local resident indices */
 long long rxmd_hip_get_bonds_device(rxmd_handle h, int flags, double bo_min, long long capacity, long long *src, long long *dst, double *bo,
                                     double *bo3, double *vec3, void *stream);
+
+/* The vector-Jacobian product of that graph with respect to the positions, on the device.
+ * grad_pos3[natoms][3] = dL/dr for L = any function of the arrays the rxmd_hip_get_bonds_device call with the same (flags, bo_min) returns on the same
+ * FORCE state; grad_bo[E] = dL/dbo, grad_bo3[3E] = dL/dbo3 or NULL, grad_vec3[3E] = dL/dvec3 or NULL: device pointers in that call's edge order.
+ * At least one of the three is given.  E must be the number of edges that call selects (the selection is made again: same flags, same stable scan,
+ * same order); otherwise RXMD_E_ARG and nothing is written.  The threshold is a selection, it is not differentiated; RXMD_BONDS_GID in flags only
+ * names which selection was made.  grad_pos3 is OVERWRITTEN, in resident order (the order of rxmd_hip_get_atoms, and the caller's order after
+ * rxmd_hip_evaluate_device); what lands on a ghost is folded onto its owner: a bond through a periodic image sends its share to the resident.
+ * The derivative of a corrected bond order reaches through the neighbour shells of both atoms; it is the force assembly of FORCE (ForceBbo +
+ * ForceBondedTerms) with the caller's coefficients in place of dE/dBO and without the index-ordered ForceD term, which is no exact derivative.  It
+ * reads what the last FORCE left and changes nothing any other entry point returns: forces, energies, stress accumulators and timers stay as they
+ * were.  No atomics: two calls on one state return the same bits.  Bond orders do not depend on the charges.
+ * Stream protocol of rxmd_hip_get_bonds_device: the engine's stream waits for what `stream` held at entry, `stream` waits for an event behind the
+ * last kernel; one host wait (for the count).
+ * RXMD_E_STATE as for rxmd_hip_get_bonds_device: no FORCE yet, or set_atoms / set_lattice / set_charges since.  Fine after rxmd_hip_step and on engines
+ * created with pqeq_path.  RXMD_E_ARG (checked first): unknown bits in flags, a non-finite bo_min, E < 0, grad_pos3 NULL, all three gradients NULL,
+ * vprocs other than 1 1 1 (the fold of the ghosts' gradients would be collective).  No counterpart in the reference. */
+int rxmd_hip_bonds_vjp_device(rxmd_handle h, int flags, double bo_min, long long E, const double *grad_bo, const double *grad_bo3,
+                              const double *grad_vec3, double *grad_pos3, void *stream);
 
 /* ---- introspection for tests, roofline accounting and the timers table (main.F90:135-182) ---- */
 typedef struct rxmd_stats {

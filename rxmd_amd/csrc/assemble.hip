@@ -180,7 +180,7 @@ void Engine::force(bool defer_host_read, bool observe_energy) {
     st.bond_overlap = 1;
     k_add_force3<<<nblk(N, 256), 256, 0, stream>>>(N, fnb[0], fnb[1], fnb[2], frc[0], frc[1], frc[2]);
     accumulate_stress(false);                            // pot.F90:65-72, before the ghost forces are folded back
-    { Timed kt(this, &st.ms_fold); fold_ghost_forces(); }
+    { Timed kt(this, &st.ms_fold); fold_ghost_forces(frc[0], frc[1], frc[2]); }
     RX_HIP(hipMemcpyAsync(h_scal + H_SCAL_PE, pe_d, sizeof(double) * SCAL_PE_N, hipMemcpyDeviceToHost, stream));
     t_force.end();
     force_pending = true;
@@ -199,7 +199,7 @@ void Engine::force(bool defer_host_read, bool observe_energy) {
   if (ff.pqeq) efield_force();                         // pot.F90:61, before ForceBondedTerms
   { Timed kt(this, &st.ms_k_assemble); assemble_forces(); }
   accumulate_stress(false);                            // pot.F90:65-72, before the ghost forces are folded back
-  { Timed kt(this, &st.ms_fold); fold_ghost_forces(); }
+  { Timed kt(this, &st.ms_fold); fold_ghost_forces(frc[0], frc[1], frc[2]); }
   t_bonded.end();
   RX_HIP(hipMemcpyAsync(h_scal + H_SCAL_PE, pe_d, sizeof(double) * SCAL_PE_N, hipMemcpyDeviceToHost, stream));
   t_force.end();

@@ -190,6 +190,11 @@ void Engine::declare_buffers() {
   b.add(dh_serve, G_DH_SERVE, Dim::Cap, 1, 0, P, never);
   b.add(bg_flag, G_BGRAPH, Dim::Cap, 1, 1, P, never);         // rxmd_hip_get_bonds_device (device_io.hip): selection flag and output offset per entry of the
   b.add(bg_off, G_BGRAPH, Dim::Cap, 1, 1, P, never);          // bond tables, capacity = bcap of the day of the call; an engine that never asks has neither
+  // rxmd_hip_bonds_vjp_device (bond_vjp.hip): per table entry the coefficients / force terms and the ccbnd term, per atom slot ccbnd and the gradient;
+  // first use allocates them, at bcap and NB of that day (Engine::bonds_vjp_device re-allocates when either has grown)
+  for (double **t : {&bv_c1, &bv_c2, &bv_c3, &bv_t}) b.add(*t, G_BVJP, Dim::Cap, 1, 0, P, never);
+  b.add(bv_cc, G_BVJP, Dim::NB, 1, 0, P, never);
+  for (int a = 0; a < 3; ++a) b.add(bv_g[a], G_BVJP, Dim::NB, 1, 0, P, never);
 }
 
 size_t Buffers::count(const Buf &b, const Engine &e) const {

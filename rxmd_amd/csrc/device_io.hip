@@ -183,15 +183,8 @@ __global__ void __launch_bounds__(256) k_bond_fill(int n, int nres, int as_gid, 
   if (vec3) { vec3[3 * e] = x[j] - x[i]; vec3[3 * e + 1] = y[j] - y[i]; vec3[3 * e + 2] = z[j] - z[i]; }   // the ghost IS the right periodic image: no minimum-image step
 }
 
-long long Engine::bonds_device(int flags, double bo_min, long long capacity, long long *src_d, long long *dst_d, double *bo_d, double *bo3_d, double *vec3_d, hipStream_t user) {
-  const bool count_only = !src_d && !dst_d && !bo_d;
-  const bool as_gid = (flags & RXMD_BONDS_GID) != 0;
-  if (flags & ~RXMD_BONDS_GID) throw EngineError(RXMD_E_ARG, "get_bonds_device: unknown bit in flags");
-  if (!std::isfinite(bo_min)) throw EngineError(RXMD_E_ARG, "get_bonds_device: bo_min must be finite");
-  if (!count_only && (!src_d || !dst_d || !bo_d)) throw EngineError(RXMD_E_ARG, "get_bonds_device: src, dst and bo go together (all three NULL: count only)");
-  if (!count_only && capacity < 0) throw EngineError(RXMD_E_ARG, "get_bonds_device: negative capacity");
-  if (!as_gid && nprocs != 1) throw EngineError(RXMD_E_ARG, "get_bonds_device: local indices need a single rank (vprocs 1 1 1); ask for global ids (RXMD_BONDS_GID)");
-  if (!atoms_set || !lists_valid) throw EngineError(RXMD_E_STATE, "no bond lists: call rxmd_hip_force first");
+// select + exclusive sum over the residents' entries, shared with the VJP of the graph (bond_vjp.hip): the same flags, the same offsets, the same count
+long long Engine::select_bonds(double bo_min) {
   if (force_pending) finish_force();               // (FORCE itself joins the bonded chain's stream and the halo stream in front of its end)
   const int n = nbonds_res;
   if (n <= 0) return 0;
@@ -209,8 +202,21 @@ long long Engine::bonds_device(int flags, double bo_min, long long capacity, lon
   size_t tb = cubtmp_bytes;
   RX_HIP(hipcub::DeviceScan::ExclusiveSum(cubtmp, tb, bg_flag, bg_off, n + 1, stream));
   RX_HIP(hipMemcpyAsync(h_cnt + 2, bg_off + n, sizeof(int), hipMemcpyDeviceToHost, stream));
-  sync_stream();                                     // the host wait of the call
-  const long long E = h_cnt[2];
+  sync_stream();
+  return h_cnt[2];
+}
+
+long long Engine::bonds_device(int flags, double bo_min, long long capacity, long long *src_d, long long *dst_d, double *bo_d, double *bo3_d, double *vec3_d, hipStream_t user) {
+  const bool count_only = !src_d && !dst_d && !bo_d;
+  const bool as_gid = (flags & RXMD_BONDS_GID) != 0;
+  if (flags & ~RXMD_BONDS_GID) throw EngineError(RXMD_E_ARG, "get_bonds_device: unknown bit in flags");
+  if (!std::isfinite(bo_min)) throw EngineError(RXMD_E_ARG, "get_bonds_device: bo_min must be finite");
+  if (!count_only && (!src_d || !dst_d || !bo_d)) throw EngineError(RXMD_E_ARG, "get_bonds_device: src, dst and bo go together (all three NULL: count only)");
+  if (!count_only && capacity < 0) throw EngineError(RXMD_E_ARG, "get_bonds_device: negative capacity");
+  if (!as_gid && nprocs != 1) throw EngineError(RXMD_E_ARG, "get_bonds_device: local indices need a single rank (vprocs 1 1 1); ask for global ids (RXMD_BONDS_GID)");
+  if (!atoms_set || !lists_valid) throw EngineError(RXMD_E_STATE, "no bond lists: call rxmd_hip_force first");
+  const int n = nbonds_res;
+  const long long E = select_bonds(bo_min);          // the host wait of the call
   if (count_only || capacity < E || E == 0) return E;
   if (!ev_io_in) { RX_HIP(hipEventCreateWithFlags(&ev_io_in, hipEventDisableTiming)); RX_HIP(hipEventCreateWithFlags(&ev_io_out, hipEventDisableTiming)); }
   RX_HIP(hipEventRecord(ev_io_in, user));            // whatever the caller's stream still does with the output arrays comes first

@@ -189,7 +189,7 @@ enum class Dim : unsigned char { Fixed, NB, Rows10, List10, Cap };   // what a b
 enum class Refill : unsigned char { Never, Whole, Ghosts };          // RXMD_POISON_ALLOC refill before a rebuild: none, the whole buffer, elements [N, NB)
 enum class Space : unsigned char { Device, Pinned, PinnedCoherent };
 // re-allocation groups.  Those before G_ON_DEMAND exist from set-up on (Buffers::alloc_setup); the others are allocated when first needed
-enum { G_SETUP, G_BOND, G_WIN, G_CELLSTART, G_LIST10, G_PARTIALS, G_ON_DEMAND, G_CUBTMP = G_ON_DEMAND, G_FFBLOB, G_PQBLOB, G_E4B, G_SEG, G_SEG_PINNED, G_XBUF, G_DH_SERVE, G_BGRAPH, G_COUNT };
+enum { G_SETUP, G_BOND, G_WIN, G_CELLSTART, G_LIST10, G_PARTIALS, G_ON_DEMAND, G_CUBTMP = G_ON_DEMAND, G_FFBLOB, G_PQBLOB, G_E4B, G_SEG, G_SEG_PINNED, G_XBUF, G_DH_SERVE, G_BGRAPH, G_BVJP, G_COUNT };
 enum : unsigned { BUF_PQEQ = 1u, BUF_RESIDENT = 2u, BUF_QEQ_F32 = 4u };   // exists only with PQEq ; resident state that grow_capacity carries over ; exists only while the fp32 matrix stream is requested (set_qeq_precision)
 struct Buf { void **pp; size_t elem; int group; Dim dim; size_t mul, add_; Fill fill; Refill refill; unsigned flags; Space space; size_t bytes; };   // bytes: what was allocated (0: nothing of ours)
 struct Buffers {
@@ -378,6 +378,14 @@ struct Engine {
   // written when capacity is smaller.  bg_flag / bg_off: its scratch, one int per table entry + 1, allocated on first use at the capacity of the bond tables
   long long bonds_device(int flags, double bo_min, long long capacity, long long *src_d, long long *dst_d, double *bo_d, double *bo3_d, double *vec3_d, hipStream_t user);
   int *bg_flag = nullptr, *bg_off = nullptr;
+  long long select_bonds(double bo_min);           // bg_flag / bg_off of the residents' entries for this threshold -> the number selected (the one host wait of either caller)
+  // rxmd_hip_bonds_vjp_device (bond_vjp.hip): the vector-Jacobian product of that graph with respect to the positions.  grad_bo / grad_bo3 / grad_vec3 are
+  // dL/d(bo, bo3, vec3) in the edge order of bonds_device(flags, bo_min); grad_pos3[N][3] = dL/dr of the residents, ghosts folded onto their owners.
+  // The assembly of assemble.hip with the caller's coefficients in place of cf1..cf3, cd = 0 and no fn*; reads what FORCE left (bo*, A0..A3, dBOp, dln*),
+  // writes its own scratch only: bv_c1..3 (per table entry: the symmetrised coefficients, then the three force-term components in place), bv_t (the
+  // ccbnd term), bv_cc and bv_g (per atom, ghost slots included); allocated on first use at the capacities of the day (bv_nb: the NB they were sized for)
+  void bonds_vjp_device(int flags, double bo_min, long long E, const double *grad_bo_d, const double *grad_bo3_d, const double *grad_vec3_d, double *grad_pos3_d, hipStream_t user);
+  double *bv_c1 = nullptr, *bv_c2 = nullptr, *bv_c3 = nullptr, *bv_t = nullptr, *bv_cc = nullptr, *bv_g[3] = {nullptr, nullptr, nullptr}; int bv_nb = 0;
   void build_ghosts_and_lists(bool qeq_prepass = false);   // COPYATOMS(MODE_COPY) + LINKEDLIST + NEIGHBORLIST + 10 A list/hessian, once per step
   void qeq_start_vectors();        // qs, qt, hs, ht of qeq.F90:36-63 and their cell-sorted copy (before the list sweep that uses them)
   int *rows_int = nullptr, *rows_bnd = nullptr; int n_bnd = 0; bool rows_split_pending = false;   // interior / boundary rows (multi-rank)
@@ -528,7 +536,7 @@ struct Engine {
   void allreduce_device(double *dev, int n, int h_stage, int site = -1);
   void ghost_build_staged();                        // stage by stage: several ranks, or one rank under RXMD_NO_STAGE_PAIRS=1
   void sorted_copy(const double2 *v);               // QCOPY1/QCOPY2 fused with the cell-sorted gather copy -> xs
-  void fold_ghost_forces();                         // CPBK
+  void fold_ghost_forces(double *fx, double *fy, double *fz);   // CPBK of a per-atom vector given by component (FORCE: frc)
   void bond_orders();
   void bonded_energies();
   void charge_halo();

@@ -639,18 +639,19 @@ void Engine::halo_staged(double *v, int ncomp) {
 }
 
 // MODE_CPBK (comm.F90:74-78,385-396,474-482): the rounds backwards, z first; inside a round the sums of the higher stage land first (6 then 5), which
-// keeps the reference's summation order 6,5,4,...  On a single rank a ghost's force goes straight to its source.
-void Engine::fold_ghost_forces() {
+// keeps the reference's summation order 6,5,4,...  On a single rank a ghost's force goes straight to its source.  The three arrays folded are the
+// caller's: FORCE passes frc, the bond-order VJP (bond_vjp.hip) its per-atom gradient -- any per-atom vector with ghost slots folds the same way.
+void Engine::fold_ghost_forces(double *fx, double *fy, double *fz) {
   const bool local = !multi(), pairs = !local && known_counts_pair();
   for (int i = 0; i < n_rounds(pairs); ++i) {
     const Round r = round_at(i, pairs, true);
     const int g0 = copyptr[r.d0 - 1], cnt = copyptr[r.d0 + r.n - 1] - g0;
     if (local) {
       for (int d = r.d0 + r.n - 1; d >= r.d0; --d)
-        if (copyptr[d] > copyptr[d - 1]) k_fold_stage<<<nblk(copyptr[d] - copyptr[d - 1], 256), 256, 0, stream>>>(copyptr[d - 1], copyptr[d], gsrc, frc[0], frc[1], frc[2]);
+        if (copyptr[d] > copyptr[d - 1]) k_fold_stage<<<nblk(copyptr[d] - copyptr[d - 1], 256), 256, 0, stream>>>(copyptr[d - 1], copyptr[d], gsrc, fx, fy, fz);
       continue;
     }
-    if (cnt > 0) k_pack_force<<<nblk(cnt, 256), 256, 0, stream>>>(g0, cnt, frc[0], frc[1], frc[2], xbuf_send);
+    if (cnt > 0) k_pack_force<<<nblk(cnt, 256), 256, 0, stream>>>(g0, cnt, fx, fy, fz, xbuf_send);
     long long nsend[2] = {0, 0}, want[2] = {0, 0}, nrecv[2];
     for (int k = 0; k < r.n; ++k) { nsend[k] = 3LL * stage_ghosts(r.d0 + k); want[k] = 3LL * stage_sends(r.d0 + k); }
     nrecv[0] = want[0]; nrecv[1] = want[1];
@@ -658,7 +659,7 @@ void Engine::fold_ghost_forces() {
     if (nrecv[0] != want[0] || nrecv[1] != want[1]) throw EngineError(RXMD_E_COMM, "returned force count does not match the stage send list");
     for (int d = r.d0 + r.n - 1; d >= r.d0; --d)      // sources are unique within a stage, not within a round
       if (stage_sends(d) > 0)
-        k_add_force<<<nblk(stage_sends(d), 256), 256, 0, stream>>>(stage_sends(d), sendidx + sendoff[d], xbuf_recv + 3LL * (sendoff[d] - sendoff[r.d0]), frc[0], frc[1], frc[2]);
+        k_add_force<<<nblk(stage_sends(d), 256), 256, 0, stream>>>(stage_sends(d), sendidx + sendoff[d], xbuf_recv + 3LL * (sendoff[d] - sendoff[r.d0]), fx, fy, fz);
   }
 }
 

@@ -261,6 +261,14 @@ class RxmdEngine:
         return self._chk(self.L.rxmd_hip_get_bonds_device(self.h, BONDS_GID if as_gid else 0, float(bo_min), int(capacity), p[0], p[1], p[2], p[3], p[4],
                                                           C.c_void_p(int(stream) or None)))
 
+    def bonds_vjp_device(self, E, grad_pos_ptr, grad_bo_ptr=0, grad_bo3_ptr=0, grad_vec_ptr=0, bo_min=0.0, as_gid=False, stream=0):
+        """the vector-Jacobian product of that graph with respect to the positions (include/rxmd_hip.h: rxmd_hip_bonds_vjp_device), device arrays given
+        as integer addresses: float64 grad_bo[E], grad_bo3[E][3], grad_vec[E][3] (0: not given; at least one is) are dL/d(bo, bo3, vec) in the edge
+        order of bonds_device(bo_min=bo_min, as_gid=as_gid) on the same FORCE state, E the count that call returns (RxmdError -1 otherwise, nothing
+        written); float64 grad_pos[natoms][3] receives dL/dpos in the order of atoms() (overwritten)"""
+        p = [C.c_void_p(int(a) or None) for a in (grad_bo_ptr, grad_bo3_ptr, grad_vec_ptr, grad_pos_ptr)]
+        self._chk(self.L.rxmd_hip_bonds_vjp_device(self.h, BONDS_GID if as_gid else 0, float(bo_min), int(E), p[0], p[1], p[2], p[3], C.c_void_p(int(stream) or None)))
+
     # ---- introspection ----
     def stats(self):
         s = RxmdStats(); self._chk(self.L.rxmd_hip_get_stats(self.h, C.byref(s))); return s.asdict()

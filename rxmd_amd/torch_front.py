@@ -10,8 +10,14 @@ a bias potential, an integrator or a correction model written in torch composes 
     e = model(pos); e.backward()        # pos.grad == -forces
     g = model.bond_graph(bo_min=0.3)    # dict(edge_index [2, E], bond_order [E], edge_vec [E, 3]) of the last evaluate, device tensors
 
+    b = model.bond_orders(pos, bo_min=0.3)   # the same graph of a fresh evaluate, DIFFERENTIABLE in pos (with energy, forces, charges)
+
 The bond-order graph (`bond_graph`, or `evaluate(pos, bond_graph=bo_min)`) is what FORCE left in the engine's bond tables, compacted on the device
-(RxmdEngine.bonds_device -> rxmd_hip_get_bonds_device).  It is NOT differentiable: bond orders and bond vectors come out as constants.
+(RxmdEngine.bonds_device -> rxmd_hip_get_bonds_device).  From those two calls it is NOT differentiable: bond orders and bond vectors come out as
+constants.  `bond_orders(pos)` returns the same arrays as outputs of one `torch.autograd.Function` whose backward is the engine's vector-Jacobian
+product (RxmdEngine.bonds_vjp_device -> rxmd_hip_bonds_vjp_device): a restraint on a bond order or a coordination number, a reaction-coordinate
+loss or a model trained on bond orders sends its gradient to pos.  The backward reads the engine's state of that evaluation, so it has to run
+before the model evaluates again (RuntimeError otherwise).
 
 Single rank, plain QEq (isQEq 0 or 1).  No second derivatives, no gradient with respect to the lattice.
 This module imports torch; `import rxmd_amd` does not import it.
@@ -56,9 +62,47 @@ class _Energy(torch.autograd.Function):
         return -forces * grad_output, None
 
 
+class _BondOrders(torch.autograd.Function):
+    """one evaluate + one graph extraction; outputs: energy, bond_order, edge_vec, bond_order_parts (None without components) -- differentiable --
+    and edge_index, forces, charges (constants).  backward: -forces g_E + the engine's VJP of (g_bo, g_parts, g_vec); an output the loss did not
+    use arrives as None and goes to the engine as NULL"""
+
+    @staticmethod
+    def forward(ctx, pos, model, bo_min, components, q0):
+        out = model.evaluate(pos.detach(), q0=q0)
+        g = model.bond_graph(bo_min=bo_min, components=components)
+        ctx.model, ctx.bo_min, ctx.serial = model, bo_min, model._evaluations
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(out["forces"])
+        ctx.mark_non_differentiable(g["edge_index"], out["forces"], out["charges"])
+        return out["energy"], g["bond_order"], g["edge_vec"], g.get("bond_order_parts"), g["edge_index"], out["forces"], out["charges"]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_energy, g_bo, g_vec, g_parts, *unused):
+        model = ctx.model
+        if ctx.serial != model._evaluations:
+            raise RuntimeError("the engine no longer holds the state these bond orders came from (evaluate / energy / bond_orders / set_lattice ran on "
+                               "the model since): call backward before the next evaluation")
+        (forces,) = ctx.saved_tensors
+        grad = None if g_energy is None else -forces * g_energy
+        given = [None if g is None else g.to(torch.float64).contiguous() for g in (g_bo, g_parts, g_vec)]
+        E = next((int(g.shape[0]) for g in given if g is not None), 0)
+        if E > 0:
+            with torch.cuda.device(model.device):
+                gpos = torch.empty((model.natoms, 3), dtype=torch.float64, device=model.device)
+                ptr = [0 if g is None else g.data_ptr() for g in given]
+                model.engine.bonds_vjp_device(E, gpos.data_ptr(), grad_bo_ptr=ptr[0], grad_bo3_ptr=ptr[1], grad_vec_ptr=ptr[2], bo_min=ctx.bo_min,
+                                              stream=torch.cuda.current_stream(model.device).cuda_stream)
+            grad = gpos if grad is None else grad + gpos
+        return grad, None, None, None, None
+
+
 class ReaxFF:
     """types: int tensor or array [N] of ffield atom types (1..nso), moved to the device once; gid: optional int64 global ids (default
     1..N); engine_kw: the keywords of RxmdEngine (isQEq, QEq_tol, NMAXQEq, device, ...)"""
+
+    _evaluations = 0      # evaluations (and lattice changes) so far: a backward of bond_orders checks that the engine still holds its state
 
     def __init__(self, ffield, lattice, types, gid=None, **engine_kw):
         self.engine = RxmdEngine(ffield, lattice, **engine_kw)      # RxmdError(-6) without a GPU, before torch is asked for one
@@ -87,6 +131,7 @@ class ReaxFF:
                 raise ValueError("q0 must be a float64 CUDA tensor of shape [%d] on %s" % (self.natoms, self.device))
             q0 = q0.detach().contiguous()
         p = pos.detach().contiguous()
+        self._evaluations += 1
         with torch.cuda.device(self.device):
             forces = torch.empty((self.natoms, 3), dtype=torch.float64, device=self.device)
             charges = torch.empty(self.natoms, dtype=torch.float64, device=self.device)
@@ -108,8 +153,8 @@ class ReaxFF:
             bond_order_parts [E, 3]    with components=True: sigma, pi, double-pi (they sum to bond_order)
         Edges are ordered by src, then by the engine's list order.  Count, allocate exactly, fill: two short device passes, one host wait each.
 
-        NOT differentiable: these are constants, no gradient reaches pos through them.  For differentiable bond lengths recover the integer image
-        shift once and recompute in torch (H = the lattice vectors as columns):
+        NOT differentiable: these are constants, no gradient reaches pos through them (bond_orders(pos) returns the same graph with gradients).  For
+        differentiable bond lengths alone, recover the integer image shift once and recompute in torch (H = the lattice vectors as columns):
             src, dst = g["edge_index"]
             shift = torch.round((g["edge_vec"] - (pos[dst] - pos[src])) @ torch.linalg.inv(H).T)       # [E, 3] integers, constants
             d = (pos[dst] - pos[src] + shift @ H.T).norm(dim=1)                                       # differentiable in pos"""
@@ -133,6 +178,26 @@ class ReaxFF:
             out["bond_order_parts"] = parts
         return out
 
+    def bond_orders(self, pos, bo_min=0.0, components=False, q0=None):
+        """One evaluate at pos and the bond-order graph of it, differentiable in pos -> dict of
+            energy           0-dim, differentiable (d energy / d pos = -forces)
+            edge_index       [2, E] int64, a constant: which entries are selected (bond_order >= bo_min) is not differentiated
+            bond_order       [E], edge_vec [E, 3], and with components=True bond_order_parts [E, 3] (sigma, pi, double-pi): differentiable
+            forces [N, 3], charges [N]   constants, as from evaluate
+        in the layout of bond_graph.  The derivative of a corrected bond order reaches through the neighbour shells of both atoms; it comes from the
+        engine (rxmd_hip_bonds_vjp_device), first derivatives only.  A coordination number is `torch.zeros(N).index_add(0, edge_index[0], bond_order)`.
+        backward() must run before the next evaluate / energy / bond_orders / set_lattice on this model: the engine keeps ONE state, and a backward
+        that finds another raises RuntimeError -- nothing is evaluated again behind the caller's back."""
+        _check_pos(pos, self.natoms, self.device)
+        bo_min = _check_bo_min(bo_min)
+        if not isinstance(components, (bool, np.bool_)):
+            raise ValueError("components must be a bool, got %s" % type(components).__name__)
+        energy, bo, vec, parts, edge, forces, charges = _BondOrders.apply(pos, self, bo_min, bool(components), q0)
+        out = dict(energy=energy, edge_index=edge, bond_order=bo, edge_vec=vec, forces=forces, charges=charges)
+        if components:
+            out["bond_order_parts"] = parts
+        return out
+
     def energy(self, pos):
         """potential energy as a differentiable function of pos: d energy / d pos = -forces (first derivatives only)"""
         return _Energy.apply(pos, self)
@@ -140,6 +205,7 @@ class ReaxFF:
     __call__ = energy
 
     def set_lattice(self, lat):
+        self._evaluations += 1
         self.engine.set_lattice(lat)
 
     def close(self):
