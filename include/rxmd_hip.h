@@ -269,7 +269,9 @@ typedef struct rxmd_stats {
   /* window form of the 10 A matrix (groups of 16 cell-sorted rows whose partners the matrix pass holds in LDS): its build per list build,
    * the number of groups, the largest window in units of 8 cell-sorted positions, 1 when the matrix pass uses it (0: the row pass) */
   double ms_k_winbuild;
-  int win_groups, win_max_units, win_in_use, reserved2;
+  int win_groups, win_max_units, win_in_use;
+  int streams_by_place;                 /* layout of the per-entry streams of the 10 A list in the last build: 1 = a row lies at its place in the cell-sorted row order of the
+                                         * window groups (RXMD_STREAMS_BY_PLACE, default, when the build has windows and its places fit), 0 = at its atom index */
   /* the window pass timed on the first placement of its streams in memory and on the one that was kept (0: no search ran; see
    * Engine::tune_window_placement, RXMD_PLACE_TRIES) */
   double place_ms_first, place_ms_kept;

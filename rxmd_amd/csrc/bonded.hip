@@ -1164,7 +1164,7 @@ __global__ void __launch_bounds__(256) k_ehb_sweep(int S10, DevFF ff, const int2
                                                     double *__restrict__ cf1, double *__restrict__ fnx, double *__restrict__ fny, double *__restrict__ fnz,
                                                     double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ fz, double *__restrict__ pe,
                                                     double *__restrict__ fsx, double *__restrict__ fsy, double *__restrict__ fsz,
-                                                    const unsigned short *__restrict__ sl10, const int *__restrict__ rpos, const int *__restrict__ win_k, const unsigned char *__restrict__ stype, int G
+                                                    const unsigned short *__restrict__ sl10, const int *__restrict__ rpos, const int *__restrict__ win_k, const unsigned char *__restrict__ stype, int G, int byplace
 #ifdef RXMD_EHB_DEBUG
                                                     , int *dbg, int lim_n, int lim_b, int lim_nb
 #endif
@@ -1198,7 +1198,7 @@ __global__ void __launch_bounds__(256) k_ehb_sweep(int S10, DevFF ff, const int2
     EHB_CHECK(2, ob, lim_b - 32, i)
     EHB_CHECK(3, n, S10 + 1, i)
     const double xi = x[i], yi = y[i], zi = z[i];
-    const size_t row = static_cast<size_t>(i) * S10;
+    const size_t row = static_cast<size_t>(byplace ? rpos[i] : i) * S10;   // (Engine::streams_by_place)
     const int *wk = SLOTS ? win_k + static_cast<size_t>(rpos[i] / WIN_ROWS) * WIN_MAXUNITS : nullptr;   // the window of the donor's group
     const int inx_l = (lane >= 1 && lane <= ff.nso && lane < 16) ? ff.inxn3hb[(ti * ff.n1 + 2) * ff.n1 + lane] : 0;
     if (lane < 16) { const DevHbP hp = ff.hb[inx_l]; s_hp[w][lane][0] = hp.r0hb; s_hp[w][lane][1] = hp.phb1; s_hp[w][lane][2] = hp.phb2; s_hp[w][lane][3] = hp.phb3; }   // (row 0 is never used: the compaction drops its candidates)
@@ -1434,7 +1434,7 @@ void Engine::bonded_energies() {
     const int ehb_grid = num_cu * (slots ? ehb_blocks_per_cu_sl : ehb_blocks_per_cu);
 #ifdef RXMD_EHB_DEBUG
     RX_HIP(hipMemsetAsync(ehb_cnt + EHB_REGIONS, 0, 4 * sizeof(int), stream));
-#define RX_EHB(SL) k_ehb_sweep<SL><<<ehb_grid, 256, 0, stream>>>(S10, dff, ehb_don, ehb_cnt, region_cap, boff, nbr, type, pos[0], pos[1], pos[2], bo0, nb10, n10, sorted_xyzi, perm, cf1, fnx, fny, fnz, frc[0], frc[1], frc[2], pe_d, fsort[0], fsort[1], fsort[2], sl10, rpos, win_k, sorted_type, G, ehb_cnt + EHB_REGIONS, N, static_cast<int>(bcap), NB)
+#define RX_EHB(SL) k_ehb_sweep<SL><<<ehb_grid, 256, 0, stream>>>(S10, dff, ehb_don, ehb_cnt, region_cap, boff, nbr, type, pos[0], pos[1], pos[2], bo0, nb10, n10, sorted_xyzi, perm, cf1, fnx, fny, fnz, frc[0], frc[1], frc[2], pe_d, fsort[0], fsort[1], fsort[2], sl10, rpos, win_k, sorted_type, G, streams_by_place ? 1 : 0, ehb_cnt + EHB_REGIONS, N, static_cast<int>(bcap), NB)
     if (slots) RX_EHB(true); else RX_EHB(false);
 #undef RX_EHB
     { int hd[EHB_REGIONS + 4]; RX_HIP(hipMemcpyAsync(hd, ehb_cnt, sizeof(hd), hipMemcpyDeviceToHost, stream)); RX_HIP(hipStreamSynchronize(stream));
@@ -1442,7 +1442,7 @@ void Engine::bonded_energies() {
       hd[4] = hd[EHB_REGIONS]; hd[5] = hd[EHB_REGIONS + 1]; hd[6] = hd[EHB_REGIONS + 2]; hd[7] = hd[EHB_REGIONS + 3];
       std::fprintf(stderr, "[ehb debug] donors %d  blocks/CU %d  first violation: code %d value %d aux %d lim %d   (N %d bcap %zu NB %d S10 %d rows10 %d)\n", hd[0], ehb_blocks_per_cu, hd[4], hd[5], hd[6], hd[7], N, bcap, NB, S10, rows10); }
 #else
-#define RX_EHB(SL) k_ehb_sweep<SL><<<ehb_grid, 256, 0, stream>>>(S10, dff, ehb_don, ehb_cnt, region_cap, boff, nbr, type, pos[0], pos[1], pos[2], bo0, nb10, n10, sorted_xyzi, perm, cf1, fnx, fny, fnz, frc[0], frc[1], frc[2], pe_d, fsort[0], fsort[1], fsort[2], sl10, rpos, win_k, sorted_type, G)
+#define RX_EHB(SL) k_ehb_sweep<SL><<<ehb_grid, 256, 0, stream>>>(S10, dff, ehb_don, ehb_cnt, region_cap, boff, nbr, type, pos[0], pos[1], pos[2], bo0, nb10, n10, sorted_xyzi, perm, cf1, fnx, fny, fnz, frc[0], frc[1], frc[2], pe_d, fsort[0], fsort[1], fsort[2], sl10, rpos, win_k, sorted_type, G, streams_by_place ? 1 : 0)
     if (slots) RX_EHB(true); else RX_EHB(false);
 #undef RX_EHB
 #endif

@@ -442,7 +442,7 @@ int rxmd_hip_get_stats(rxmd_handle h, rxmd_stats *out) {
     }
     e.st.natoms = e.N;
     e.st.n_boundary_rows = (e.multi() && e.lists_valid && !e.rows_split_pending_invalid()) ? e.n_bnd : 0;
-    e.st.win_groups = e.win_groups; e.st.win_max_units = e.win_maxunits; e.st.win_in_use = e.win_used ? 1 : 0;
+    e.st.win_groups = e.win_groups; e.st.win_max_units = e.win_maxunits; e.st.win_in_use = e.win_used ? 1 : 0; e.st.streams_by_place = (e.lists_valid && e.streams_by_place) ? 1 : 0;
     // the matrix pass is timed on a sample of its launches (Engine::qeq): average of the timed ones x all of them
     e.st.spmv_launches_timed = e.pass_timed_n;
     e.st.ms_qeq_spmv = e.pass_timed_n > 0 ? e.pass_timed_ms / static_cast<double>(e.pass_timed_n) * static_cast<double>(e.st.spmv_launches) : 0.0;
@@ -516,8 +516,10 @@ int rxmd_hip_debug_get(rxmd_handle h, int what, double *out, int capacity) {
         std::vector<int> c(N); RX_HIP(hipMemcpy(c.data(), e.n10, sizeof(int) * N, hipMemcpyDeviceToHost));
         for (int &v : c) v &= rxmd::N10_COUNT;
         std::vector<double> row(e.S10);
+        std::vector<int> place(e.streams_by_place ? N : 0);        // streams by place: atom -> row of the streams (Engine::stream_rpos)
+        if (e.streams_by_place && N > 0) RX_HIP(hipMemcpy(place.data(), e.rpos, sizeof(int) * N, hipMemcpyDeviceToHost));
         for (int i = 0; i < N; ++i) {
-          RX_HIP(hipMemcpy(row.data(), e.hess + static_cast<size_t>(i) * e.S10, sizeof(double) * c[i], hipMemcpyDeviceToHost));
+          RX_HIP(hipMemcpy(row.data(), e.hess + static_cast<size_t>(e.streams_by_place ? place[i] : i) * e.S10, sizeof(double) * c[i], hipMemcpyDeviceToHost));
           double s = 0; for (int k = 0; k < c[i]; ++k) s += row[k];
           out[i] = s;
         }
@@ -556,8 +558,9 @@ int rxmd_hip_debug_get(rxmd_handle h, int what, double *out, int capacity) {
           const int i = rs[r], g = static_cast<int>(r / rxmd::WIN_ROWS);
           if (i < 0 || i >= N) continue;                           // unused row of a cell column's last group
           const int cnt = c[i] & rxmd::N10_COUNT;
-          RX_HIP(hipMemcpy(ent.data(), e.nb10 + static_cast<size_t>(i) * e.S10, sizeof(int) * cnt, hipMemcpyDeviceToHost));
-          RX_HIP(hipMemcpy(sl.data(), e.sl10 + static_cast<size_t>(i) * e.S10, sizeof(unsigned short) * cnt, hipMemcpyDeviceToHost));
+          const size_t srow = e.streams_by_place ? r : static_cast<size_t>(i);      // the row of the streams: the place, or the atom
+          RX_HIP(hipMemcpy(ent.data(), e.nb10 + srow * e.S10, sizeof(int) * cnt, hipMemcpyDeviceToHost));
+          RX_HIP(hipMemcpy(sl.data(), e.sl10 + srow * e.S10, sizeof(unsigned short) * cnt, hipMemcpyDeviceToHost));
           int good = 0;
           for (int k = 0; k < cnt; ++k) {
             const unsigned en = static_cast<unsigned>(ent[k]);

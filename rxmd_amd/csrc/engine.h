@@ -170,6 +170,8 @@ __device__ inline double wave_sum64(double v) {
 #endif
 constexpr int WIN_ROWS = WIN_ROWS_DEF;   // rows of a window group = wavefronts of a workgroup of the window pass (measured: 8 -> see NOTES.md 3)
 constexpr int WIN_UNIT = 8;         // cell-sorted positions per window unit (8 x 16 bytes = one 128-byte line of the sorted vector)
+constexpr int WIN_BP_MIN_STRIDE = 384;   // streams by place (Engine::streams_by_place) need a row stride of at least 3 x 128 entries: the window pass then requests the first
+                                        // batch of a place -- up to three register sets of 128 entries -- without a bound test (k_spmv_win, BP)
 constexpr int WIN_MAXUNITS = 448;   // units a group's descriptor holds: 3,584 slots = 56 KB of LDS (two workgroups per CU)
 constexpr int WIN_BMW = 2048;       // 64-bit words of the coverage map the build kernel keeps in LDS: a group's positions may span 2048 x 64 x 8 = 1 M
 
@@ -485,6 +487,14 @@ struct Engine {
   static size_t win_groups_bound_for(const Grid &g, long long n) { return static_cast<size_t>(n) / WIN_ROWS + static_cast<size_t>(g.n[0]) * g.n[1] + 1; }
   double qeq_iters_smooth = -1.0;               // running mean of the CG iterations per QEq call (the exit test of qeq.F90:114-115 lets single calls stop after two or three)
   bool win_valid = false, win_used = false;    // win_used: the last matrix pass was a window pass
+  // Layout of the per-entry streams of the 10 A list (nb10, hess, hess32, sl10, hsc) of the current build: row r of the streams belongs to the resident at
+  // PLACE r of rows_sorted (group * WIN_ROWS + wavefront of the window pass) instead of to atom r -- a window kernel then knows the address of its row's
+  // streams from its group number alone and requests them before it has read rows_sorted.  Decided by the sweep itself from the words of its build
+  // (k_list10: no window overflow, places <= place_cap, row stride >= WIN_BP_MIN_STRIDE) and repeated by the host from the same words; every reader that has the atom translates through
+  // rpos (stream_rpos(): nullptr = atom layout).  The places of a short last group are never written: readers mask them by the row length.
+  bool streams_by_place = false;
+  int stream_place_cap() const;                // rows10 with RXMD_STREAMS_BY_PLACE on, 0 (atom layout) otherwise
+  const int *stream_rpos() const { return streams_by_place ? rpos : nullptr; }
   void halo_refresh(double2 *v2, double *v1);       // QCOPY1/QCOPY2: ghosts <- owners (self exchange, resolved roots)
   void halo_staged(double *v, int ncomp);           // the same through the six-stage exchange (multi-rank)
   // The six exchange stages are walked in rounds (exchange.hip): a round is one stage, or the + and - stage of an axis together.  Ghost build and

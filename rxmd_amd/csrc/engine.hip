@@ -636,6 +636,7 @@ void Engine::build_ghosts_and_lists(bool qeq_prepass) {
   win_groups = h_err[8];                               // groups of this build (build_windows; the sweep ran over the host-side bound)
   max_row10 = h_err[3]; min_row10 = std::min(h_err[4], h_err[3]);   // longest / shortest 10 A row of this build (k_list10)
   win_maxunits = h_err[5]; win_valid = win_groups > 0 && h_err[6] == 0 && win_maxunits > 0 && (!multi() || (win_nbnd >= 0 && win_nbnd <= win_groups)) && !opt.spmv_no_win;   // window form of the matrix (build_windows)
+  { const int cap = stream_place_cap(); streams_by_place = cap > 0 && S10 >= WIN_BP_MIN_STRIDE && h_err[6] == 0 && static_cast<long long>(win_groups) * WIN_ROWS <= cap; }   // the sweep's own test (k_list10), on the same words
   lists_valid = true;
   if (!nb10_valid && !win_valid) require_nb10();       // the windows were lost in a build that counted on them: the row forms need the 4-byte entries (lists.hip: needs_nb10)
   collect_timers();

@@ -276,7 +276,7 @@ __global__ void __launch_bounds__(64 * L10_ROWS) k_list10(int N, int S10, Grid g
                                                  double *__restrict__ hsc, double4 *__restrict__ pqrow,
                                                  const double2 *__restrict__ xs0, double2 *__restrict__ s_all, double2 *__restrict__ s_gh, int *__restrict__ rowflag,
                                                  const int *__restrict__ rows_sorted, unsigned short *__restrict__ sl10, const int *__restrict__ rowcols, const int *__restrict__ grp_base, int *__restrict__ gflag,
-                                                 float *__restrict__ hess32 = nullptr) {
+                                                 float *__restrict__ hess32 = nullptr, int place_cap = 0) {
   __shared__ int s_q[L10_ROWS][128];     // accepted candidates: (stencil column of the row << 20 | candidate number in the row): position, atom, type and distance come back from the staged copy
   __shared__ int s_K[L10_ROWS][32], s_E[L10_ROWS][32], s_L[L10_ROWS][32];  // per stencil column of a row: first sorted position of its run - candidates before it / slot base of the column in the group's window / the same as s_K for the staged copy
   __shared__ int s_ix2[256];             // inxn2 row of the row's type would do; the whole (n1 x n1) table is 64-256 words
@@ -295,7 +295,11 @@ __global__ void __launch_bounds__(64 * L10_ROWS) k_list10(int N, int S10, Grid g
   // rows in the order of the window groups (cell-sorted: the rows of a workgroup test nearly the same candidates); the launch covers the
   // host's bound of the group count, err[8] = the groups of this build
   const int ridx = xcd_swizzle(blockIdx.x, gridDim.x) * L10_ROWS + w;
-  if (ridx - w >= err[8] * WIN_ROWS) return;  // (the whole workgroup: WIN_ROWS is a multiple of L10_ROWS)
+  const int ngroups = err[8];
+  if (ridx - w >= ngroups * WIN_ROWS) return; // (the whole workgroup: WIN_ROWS is a multiple of L10_ROWS)
+  // streams by place (engine.h: streams_by_place): this build has its windows (k_win_columns, in front of this kernel, reported no overflow) and its places
+  // fit the rows the streams were sized for -- the host repeats the test on the same words once it has read them
+  const bool byplace = place_cap > 0 && S10 >= WIN_BP_MIN_STRIDE && err[6] == 0 && ngroups * WIN_ROWS <= place_cap;
   const int i_raw = rows_sorted[ridx];
   const bool rowlive = i_raw < N;             // false: unused row of a cell column's last group -- the wavefront stays for the barriers and the staging
   const int i = rowlive ? i_raw : 0;
@@ -305,7 +309,7 @@ __global__ void __launch_bounds__(64 * L10_ROWS) k_list10(int N, int S10, Grid g
   int *cK = s_K[w], *cE = s_E[w], *cL = s_L[w];
   const double xi = x[i], yi = y[i], zi = z[i];
   const int ti = type[i];
-  const size_t row = static_cast<size_t>(i) * S10;
+  const size_t row = static_cast<size_t>(byplace ? ridx : i) * S10;       // (an unused place of a short group is never written: the wavefront leaves below)
   double sni[3] = {0.0, 0.0, 0.0};
   if (!ORTHO) ref_norm(rm, xi, yi, zi, sni);
   double sxi = 0.0, syi = 0.0, szi = 0.0, Zi = 0.0, p_f = 0.0, p_hz = 0.0, p_bz = 0.0, p_ss = 0.0;
@@ -625,6 +629,12 @@ bool Engine::needs_nb10(bool selfcheck) const {
 #endif
   return nb10_sticky || opt.nb10_always || ff.pqeq || selfcheck || opt.spmv_win == 0 || opt.nonbond_win == 0 || opt.spmv_no_win || !win_valid;
 }
+int Engine::stream_place_cap() const {
+#ifdef RXMD_EXPERIMENTS
+  return 0;                                        // (the probes of experiments.hip index the streams by atom)
+#endif
+  return opt.streams_by_place != 0 ? rows10 : 0;
+}
 void Engine::require_nb10() {
   if (nb10_valid) return;
   nb10_sticky = true;
@@ -655,7 +665,7 @@ void Engine::build_list10() {
 #define RX_LIST10_F(SC, PQF, OR, F)                                                                                                            \
   k_list10<SC, PQF, OR, F><<<std::max(win_groups, 1) * (WIN_ROWS / L10_ROWS_LAUNCH), 64 * L10_ROWS_LAUNCH, 0, stream>>>(N, S10, grid, rmesh, dff, cellid, cellstart, sorted_xyzi, pos[0], pos[1], pos[2], spos[0], spos[1], spos[2], type, gid, \
                                                     nb10_w, hess, n10, d_err, sorted_shl, shl[0], shl[1], shl[2], hsc, pqrow, sums_from_list ? xs : nullptr, sall, sgh, multi() ? flags : nullptr, \
-                                                    rows_sorted, sl10, rowcols, grp_base, gflag, F ? hess32 : nullptr)
+                                                    rows_sorted, sl10, rowcols, grp_base, gflag, F ? hess32 : nullptr, stream_place_cap())
   const bool f32 = qeq_bits_req == 32 && !ff.pqeq && hess32 != nullptr;   // the values of this build are rounded to REAL(4), in both streams
   win_valid = false;
   build_windows();

@@ -61,7 +61,8 @@ template <bool ENERGY>
 __global__ void __launch_bounds__(64 * NB_WPB) k_nonbond(int N, int S10, DevFF ff, const int *__restrict__ nb10, const int *__restrict__ n10,
                                                   const double4 *__restrict__ pk, const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
                                                   const double *__restrict__ q, const int *__restrict__ type,
-                                                  double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ fz, double *__restrict__ pe, int assign) {
+                                                  double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ fz, double *__restrict__ pe, int assign,
+                                                  const int *__restrict__ rplace) {     // rplace != nullptr: the streams are laid out by place (Engine::stream_rpos)
   __shared__ double sm[NB_WPB][3], sv[NB_WPB][6];
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));   // wave-uniform -> scalar registers
   if (threadIdx.x < 6 * NB_WPB) sv[threadIdx.x / 6][threadIdx.x % 6] = 0.0;
@@ -72,7 +73,7 @@ __global__ void __launch_bounds__(64 * NB_WPB) k_nonbond(int N, int S10, DevFF f
     const double xi = x[i], yi = y[i], zi = z[i], qi = q[i];
     const int ti = type[i];
     const int n = n10[i] & N10_COUNT;
-    const size_t row = static_cast<size_t>(i) * S10;
+    const size_t row = static_cast<size_t>(rplace ? rplace[i] : i) * S10;
     const int *ix2 = ff.inxn2 + ti * ff.n1;
     NbAcc acc = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};      // force, pair virial (see the stress note at the end of the row), energies
     for (int k0 = lane; k0 < n; k0 += 64 * NB_UNR) {
@@ -133,7 +134,7 @@ __global__ void __launch_bounds__(64 * WIN_ROWS, 8) k_nonbond_win(int N, int G, 
                                                                 const double4 *__restrict__ pk, const unsigned char *__restrict__ stype,
                                                                 const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
                                                                 const double *__restrict__ q, const int *__restrict__ type,
-                                                                double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ fz, double *__restrict__ pe, int assign) {
+                                                                double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ fz, double *__restrict__ pe, int assign, int byplace) {
   extern __shared__ double4 s_p[];                 // window: slot -> (x, y, z, q) ...
   unsigned char *s_t = reinterpret_cast<unsigned char *>(s_p + static_cast<size_t>(maxunits) * WIN_UNIT);   // ... and the atom type
   __shared__ double sm[WIN_ROWS][3], sv[WIN_ROWS][6];
@@ -156,7 +157,7 @@ __global__ void __launch_bounds__(64 * WIN_ROWS, 8) k_nonbond_win(int N, int G, 
     const double xi = x[i], yi = y[i], zi = z[i], qi = q[i];
     const int ti = type[i];
     const int n = n10[i] & N10_COUNT;
-    const size_t row = static_cast<size_t>(i) * S10;
+    const size_t row = static_cast<size_t>(byplace ? ridx : i) * S10;      // (Engine::streams_by_place)
     const int *ix2 = ff.inxn2 + ti * ff.n1;
     NbAcc acc = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int k0 = lane; k0 < n; k0 += 64 * NB_UNR) {
@@ -221,15 +222,15 @@ void Engine::nonbonded(bool to_fnb, bool energy) {
   const size_t lds = static_cast<size_t>(units) * WIN_UNIT * (sizeof(double4) + 1) + 16;
   if (win_valid && win_env && !list_selfcheck) {
 #define RX_NB_WIN(EN) k_nonbond_win<EN><<<win_groups, 64 * WIN_ROWS, lds, stream>>>(N, G, S10, dff, sl10, n10, rows_sorted, win_k, win_cnt, units, sorted_xyzi, sorted_type, pos[0], pos[1], pos[2], q, type, \
-                                                                 f0, f1, f2, scal + SCAL_PE, assign)
+                                                                 f0, f1, f2, scal + SCAL_PE, assign, streams_by_place ? 1 : 0)
     if (energy) RX_NB_WIN(true); else RX_NB_WIN(false);
 #undef RX_NB_WIN
     RX_HIP(hipGetLastError());
     return;
   }
   require_nb10();                                  // the row form reads the 4-byte entries
-  if (energy) k_nonbond<true><<<nblk(N, NB_WPB), 64 * NB_WPB, 0, stream>>>(N, S10, dff, nb10, n10, sorted_xyzi, pos[0], pos[1], pos[2], q, type, f0, f1, f2, scal + SCAL_PE, assign);
-  else k_nonbond<false><<<nblk(N, NB_WPB), 64 * NB_WPB, 0, stream>>>(N, S10, dff, nb10, n10, sorted_xyzi, pos[0], pos[1], pos[2], q, type, f0, f1, f2, scal + SCAL_PE, assign);
+  if (energy) k_nonbond<true><<<nblk(N, NB_WPB), 64 * NB_WPB, 0, stream>>>(N, S10, dff, nb10, n10, sorted_xyzi, pos[0], pos[1], pos[2], q, type, f0, f1, f2, scal + SCAL_PE, assign, stream_rpos());
+  else k_nonbond<false><<<nblk(N, NB_WPB), 64 * NB_WPB, 0, stream>>>(N, S10, dff, nb10, n10, sorted_xyzi, pos[0], pos[1], pos[2], q, type, f0, f1, f2, scal + SCAL_PE, assign, stream_rpos());
 }
 
 }  // namespace rxmd

@@ -53,7 +53,8 @@ __global__ void __launch_bounds__(256) k_shell_update(int N, int S10, DevFF ff, 
                                                        const double4 *__restrict__ pk, const double4 *__restrict__ sorted_shl,
                                                        const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z, const int *__restrict__ type,
                                                        const double *__restrict__ sx, const double *__restrict__ sy, const double *__restrict__ sz,
-                                                       double *__restrict__ nx, double *__restrict__ ny, double *__restrict__ nz, int edir, double efield) {
+                                                       double *__restrict__ nx, double *__restrict__ ny, double *__restrict__ nz, int edir, double efield,
+                                                       const int *__restrict__ rplace) {   // rplace != nullptr: the streams are laid out by place (Engine::stream_rpos)
   const int lane = threadIdx.x & 63;
   const int i = xcd_swizzle(blockIdx.x, gridDim.x) * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
   if (i >= N) return;
@@ -62,7 +63,7 @@ __global__ void __launch_bounds__(256) k_shell_update(int N, int S10, DevFF ff, 
   const double hx = x[i] + s0, hy = y[i] + s1, hz = z[i] + s2;      // shell position
   const double Zi = ff.Zpq[ti], Ki = ff.Kspq[ti];
   const int n = n10[i] & N10_COUNT;
-  const size_t row = static_cast<size_t>(i) * S10;
+  const size_t row = static_cast<size_t>(rplace ? rplace[i] : i) * S10;
   double f0 = 0.0, f1 = 0.0, f2 = 0.0;
   constexpr int SU = 8;                                              // entries per lane and pass, all entry words requested first (as k_nonbond)
   for (int k0 = lane; k0 < n; k0 += 64 * SU) {
@@ -111,7 +112,7 @@ void Engine::pqeq_update_shells() {
   // new shells into scratch (every row reads its partners' old shells), then copy back
   require_nb10();
   k_shell_update<<<nblk(N, 4), 256, 0, stream>>>(N, S10, dff, nb10, n10, sorted_xyzi, sorted_shl, pos[0], pos[1], pos[2], type, shl[0], shl[1], shl[2], cds, cd, cc_,
-                                                cfg.efield_dir, cfg.efield_strength * 23.060538);
+                                                cfg.efield_dir, cfg.efield_strength * 23.060538, stream_rpos());
   double *tmp[3] = {cds, cd, cc_};
   for (int a = 0; a < 3; ++a) RX_HIP(hipMemcpyAsync(shl[a], tmp[a], sizeof(double) * N, hipMemcpyDeviceToDevice, stream));
   pqeq_sorted_shells();            // FORCE's MODE_COPY carries the moved shells to the ghosts (pot.F90:28)
@@ -126,7 +127,7 @@ __global__ void __launch_bounds__(256) k_nonbond_pqeq(int N, int S10, DevFF ff, 
                                                        const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
                                                        const double *__restrict__ q, const int *__restrict__ type,
                                                        const double *__restrict__ sx, const double *__restrict__ sy, const double *__restrict__ sz,
-                                                       double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ fz, double *__restrict__ pe) {
+                                                       double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ fz, double *__restrict__ pe, const int *__restrict__ rplace) {
   __shared__ double sm[4][3], sv[4][6];
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
   if (threadIdx.x < 24) sv[threadIdx.x / 6][threadIdx.x % 6] = 0.0;
@@ -139,7 +140,7 @@ __global__ void __launch_bounds__(256) k_nonbond_pqeq(int N, int S10, DevFF ff, 
     const int ti = type[i];
     const double Zi = ff.Zpq[ti], qic = qi + Zi;
     const int n = n10[i] & N10_COUNT;
-    const size_t row = static_cast<size_t>(i) * S10;
+    const size_t row = static_cast<size_t>(rplace ? rplace[i] : i) * S10;
     const int *ix2 = ff.inxn2 + ti * ff.n1;
     double f0 = 0.0, f1 = 0.0, f2 = 0.0;
     double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0, v4 = 0.0, v5 = 0.0;   // pair virial (stress note in nonbonded.hip)
@@ -222,7 +223,7 @@ void Engine::efield_force() {
 void Engine::nonbonded_pqeq() {
   require_nb10();
   k_nonbond_pqeq<<<nblk(N, 4), 256, 0, stream>>>(N, S10, dff, nb10, n10, sorted_xyzi, sorted_shl, pos[0], pos[1], pos[2], q, type, shl[0], shl[1], shl[2],
-                                                frc[0], frc[1], frc[2], scal + SCAL_PE);
+                                                frc[0], frc[1], frc[2], scal + SCAL_PE, stream_rpos());
 }
 
 }  // namespace rxmd

@@ -377,6 +377,7 @@ Engine::WinInstance Engine::win_instance() const {
 WinPassArgs Engine::win_args(bool roword) const {
   WinPassArgs a{N, G, S10, dff, sl10, hess, hess32, n10, rows_sorted, win_k, win_cnt, xs, hst, gst, qst, q, type, scal, partials, wall, wgh, hsc, pqrow,
                 nullptr, win_groups, 0, nullptr, win_flag, 0, win_maxunits, stream};
+  a.byplace = streams_by_place;
   if (roword) { a.n10 = r_n10; a.type = r_type; a.hst = r_hst; a.gst = r_gst; a.rs_all = r_wall; a.rs_gh = r_wgh; a.roword = 1; }   // per-row operands of the tail by the row's place in rows_sorted (MODE_HSH only)
   return a;
 }
@@ -418,6 +419,7 @@ int Engine::matrix_pass(const PassCall &c) {
     return a.ngroups;
   }
   RowPassArgs a = row_args();
+  a.rplace = stream_rpos();
   a.rs_all = c.ra; a.rs_gh = c.rg; a.rowlist = c.rowlist; a.nrows = c.nrows; a.pbase = c.pbase; a.stopflag = c.stopflag;
   st.spmv_nstep = 0; st.spmv_var = 0;
   qeq_bits_used = 64;                          // (with 32 requested: the double stream holds the same rounded values)

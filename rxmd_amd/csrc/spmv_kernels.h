@@ -65,7 +65,8 @@ __global__ void __launch_bounds__(1024) k_spmv(int N, int S10, DevFF ff, const i
                                                const double *__restrict__ scal, double *__restrict__ partials,
                                                double2 *__restrict__ rs_all, double2 *__restrict__ rs_gh,
                                                const double *__restrict__ hsc, const double4 *__restrict__ pqrow, int swz,
-                                               const int *__restrict__ rowlist, int nrows, int pbase, const double *__restrict__ stopflag) {
+                                               const int *__restrict__ rowlist, int nrows, int pbase, const double *__restrict__ stopflag,
+                                               const int *__restrict__ rplace = nullptr) {           // rplace != nullptr: the streams are laid out by place (Engine::stream_rpos)
   if (stopflag && *stopflag != 0.0) return;        // run-ahead CG loop: the iteration this launch belongs to was decided not to happen (scalar_algebra stage 6)
   // rowlist != nullptr: this launch covers nrows rows named by the list (interior or boundary rows of a multi-rank domain);
   // its workgroups write their partial sums behind the pbase workgroups of the other launch
@@ -81,7 +82,7 @@ __global__ void __launch_bounds__(1024) k_spmv(int N, int S10, DevFF ff, const i
   __shared__ double s_row[16][4];
   const int wave_in_wg = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
   if (row < N) {
-    const size_t base = static_cast<size_t>(row) * S10;
+    const size_t base = static_cast<size_t>(rplace ? rplace[row] : row) * S10;
     unsigned e[UNR];
     double h[UNR], c[UNR];
     // one batch of the row's streams (entry, hessian value, PQEq: shell-core value) for entries [kb, kb + 256) below `bound`
@@ -178,7 +179,11 @@ constexpr int WIN_PREFETCH = 2, WIN_LEAN = 4;
 template <class VT> struct WinVal;
 template <> struct WinVal<double> { typedef double2 pair; static __device__ inline pair make(double a, double b) { return make_double2(a, b); } };
 template <> struct WinVal<float> { typedef float2 pair; static __device__ inline pair make(float a, float b) { return make_float2(a, b); } };
-template <int MODE, bool STORE, bool PQ, int NSTEP = 2, int VAR = 0, class VT = double>      // VAR = FORM bits; VAR & 2: the second batch of a row is requested before the workgroup's barrier (below); VAR & 4: groups without a ghost partner skip the ghost-column sums (below); the default of plain QEq is 6.  NSTEP x 128 entries of a row in flight per register set (2; 3 = every row of at most 384 entries is one trip, the choice for water in rounds 4-5 -- 1.478 against 1.529 ms then, 1.61 against 1.58 since round 6, no longer the default; 1 for PQEq, whose third stream doubles a set); VAR: variants under measurement, compiled side by side and timed by debug tap 104
+// BP (streams by place, engine.h: streams_by_place): the row's streams lie at its PLACE ridx = group * WIN_ROWS + wavefront, so their address needs nothing
+// but the group number and the first batch is requested at the top of the wavefront -- behind the loads of the window descriptor (a wavefront's vector
+// loads return in order: the descriptor must not wait for the streams) and next to the scalar loads of round trip 1, instead of behind them.  An unused
+// place of a short group is read like any other (it lies inside the streams: places <= rows) and masked by its row length 0, by assignment.
+template <int MODE, bool STORE, bool PQ, int NSTEP = 2, int VAR = 0, class VT = double, bool BP = false>      // VAR = FORM bits; VAR & 2: the second batch of a row is requested before the workgroup's barrier (below); VAR & 4: groups without a ghost partner skip the ghost-column sums (below); the default of plain QEq is 6.  NSTEP x 128 entries of a row in flight per register set (2; 3 = every row of at most 384 entries is one trip, the choice for water in rounds 4-5 -- 1.478 against 1.529 ms then, 1.61 against 1.58 since round 6, no longer the default; 1 for PQEq, whose third stream doubles a set); VAR: variants under measurement, compiled side by side and timed by debug tap 104
 __global__ void __launch_bounds__(64 * WIN_ROWS, 8) k_spmv_win(int N, int G, int S10, DevFF ff, const unsigned short *__restrict__ sl10, const VT *__restrict__ hess, const int *__restrict__ n10,
                                                             const int *__restrict__ rows_sorted, const int *__restrict__ win_k, const int *__restrict__ win_cnt,
                                                             const double2 *__restrict__ xv, const double2 *__restrict__ hst, double2 *__restrict__ gst,
@@ -209,29 +214,48 @@ __global__ void __launch_bounds__(64 * WIN_ROWS, 8) k_spmv_win(int N, int G, int
   // Round trip 1: everything that needs only the group number -- the row of this wavefront, the window's size, the first positions of the
   // window units this thread will copy (two rounds of 1,024 slots cover 256 units; the descriptor row is WIN_MAXUNITS long whatever the count).
   const int ridx = grp * WIN_ROWS + wave;
-  const int row = min(rows_sorted[ridx], N);        // (a cell column's last group may be short: those slots hold a sentinel >= N)
-  const int nslots = WIN_UNIT * win_cnt[grp];
   const int *wk = win_k + static_cast<size_t>(grp) * WIN_MAXUNITS;
   const int t0 = threadIdx.x, t1 = threadIdx.x + NT;
   const int wk0 = wk[t0 / WIN_UNIT], wk1 = wk[t1 / WIN_UNIT];                      // (t1 / 8 < 256 <= WIN_MAXUNITS)
+  hpair v[STEPS]; double2 c[STEPS]; unsigned ss[STEPS];
+  if (BP) {
+    // the row's first batch, whatever the row (and whether the place holds one): nothing of it depends on round trip 1.  UNCONDITIONAL loads (the
+    // layout guarantees a stride of WIN_BP_MIN_STRIDE >= 128 x STEPS entries: all of them lie inside the place): behind a bound test the compiler
+    // cannot count these loads, and the wait for the window descriptor in front of them would wait for the streams as well (s_waitcnt vmcnt(1)
+    // instead of vmcnt(2 x STEPS + 1)).  The scalar loads of round trip 1 are kept BEHIND the request (below): scalar loads return in
+    // any order, so the one wait for the kernel arguments of the request (stride, stream pointers) would otherwise be a wait for round trip 1.
+    static_assert(128 * STEPS <= WIN_BP_MIN_STRIDE, "the first batch of a place is requested without a bound test");
+    const size_t pbase_ = static_cast<size_t>(ridx) * S10;
+    const h2v *ph = reinterpret_cast<const h2v *>(hess + pbase_);
+    const d2v *pc = reinterpret_cast<const d2v *>(PQ ? hsc + pbase_ : nullptr);
+    const unsigned *ps = reinterpret_cast<const unsigned *>(sl10 + pbase_);
+#pragma unroll
+    for (int u = 0; u < STEPS; ++u) {
+      const int k2 = 64 * u + lane;                                // pair index
+      const h2v t2 = __builtin_nontemporal_load(ph + k2); v[u] = WinVal<VT>::make(t2.x, t2.y);
+      ss[u] = __builtin_nontemporal_load(ps + k2);
+      if (PQ && (MODE == MODE_GRAD || STORE)) { const d2v t3 = __builtin_nontemporal_load(pc + k2); c[u] = make_double2(t3.x, t3.y); }
+    }
+  }
+  // BP: the three scalar loads of round trip 1 -- row, window size, ghost flag of the group -- issued together BEHIND the request and waited for once
+  // (left to the compiler they came out either in front of the request's own kernel-argument wait, or as three dependent round trips)
+  int rt1_row = 0, rt1_cnt = 0, rt1_flag = 1;
+  if constexpr (BP) {
+    const int *p_row = rows_sorted + ridx, *p_cnt = win_cnt + grp, *p_flag = gflags ? gflags + grp : win_cnt + grp;
+    asm volatile("s_load_dword %0, %3, 0x0\n\ts_load_dword %1, %4, 0x0\n\ts_load_dword %2, %5, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(rt1_row), "=&s"(rt1_cnt), "=&s"(rt1_flag) : "s"(p_row), "s"(p_cnt), "s"(p_flag) : "memory");
+  } else { rt1_row = rows_sorted[ridx]; rt1_cnt = win_cnt[grp]; }
+  const int row = min(rt1_row, N);                  // (a cell column's last group may be short: those slots hold a sentinel >= N)
+  const int nslots = WIN_UNIT * rt1_cnt;
   const bool live = row < N;
 #ifdef RXMD_EXPERIMENTS
-  const size_t base = static_cast<size_t>(live ? ((VAR & WIN_RANKROWS) ? ridx : row) : 0) * S10;       // (VAR & 1, experiment: the streams' rows in cell-sorted order)
+  const size_t base = static_cast<size_t>(BP ? ridx : (live ? ((VAR & WIN_RANKROWS) ? ridx : row) : 0)) * S10;       // (VAR & 1, experiment: the streams' rows in cell-sorted order)
 #else
-  const size_t base = static_cast<size_t>(live ? row : 0) * S10;
+  const size_t base = static_cast<size_t>(BP ? ridx : (live ? row : 0)) * S10;
 #endif
   const h2v *hv2 = reinterpret_cast<const h2v *>(hess + base);
   const d2v *cv2 = reinterpret_cast<const d2v *>(PQ ? hsc + base : nullptr);
   const unsigned *sl2 = reinterpret_cast<const unsigned *>(sl10 + base);
-  // VAR & 4: a group none of whose rows has a ghost partner (gflags[grp] == 0: three groups in four of a large domain) takes a body WITHOUT the
-  // ghost-column sums -- two selects and four FMAs of the twelve vector instructions per pair of entries, and two of the four reductions.  The flag
-  // rides with round trip 1 and the choice is ONE scalar branch per workgroup around two complete copies of everything below (round 6: as two loops
-  // inside one body the compiler kept the first batches alive for "the other loop" and paid with folded spills under the 64-register cap -- 48 B of
-  // scratch per lane, 20 after the register sets took turns, 0 now).
-  const bool gh = !((VAR & WIN_LEAN) != 0 && !PQ && gflags != nullptr) || gflags[grp] != 0;
-  auto whole = [&](auto ghc) {
-  constexpr bool GHC = decltype(ghc)::value;
-  hpair v[STEPS]; double2 c[STEPS]; unsigned ss[STEPS];
   auto request = [&](int kb, int bound) {          // entries kb + 128 u + 2 lane and the next one
 #pragma unroll
     for (int u = 0; u < STEPS; ++u) {
@@ -242,13 +266,21 @@ __global__ void __launch_bounds__(64 * WIN_ROWS, 8) k_spmv_win(int N, int G, int
       if (PQ && (MODE == MODE_GRAD || STORE)) { if (ok) { const d2v t2 = __builtin_nontemporal_load(cv2 + (k >> 1)); c[u] = make_double2(t2.x, t2.y); } else c[u] = make_double2(0.0, 0.0); }
     }
   };
+  // VAR & 4: a group none of whose rows has a ghost partner (gflags[grp] == 0: three groups in four of a large domain) takes a body WITHOUT the
+  // ghost-column sums -- two selects and four FMAs of the twelve vector instructions per pair of entries, and two of the four reductions.  The flag
+  // rides with round trip 1 and the choice is ONE scalar branch per workgroup around two complete copies of everything below (round 6: as two loops
+  // inside one body the compiler kept the first batches alive for "the other loop" and paid with folded spills under the 64-register cap -- 48 B of
+  // scratch per lane, 20 after the register sets took turns, 0 now).
+  const bool gh = !((VAR & WIN_LEAN) != 0 && !PQ && gflags != nullptr) || (BP ? rt1_flag : gflags[grp]) != 0;
+  auto whole = [&](auto ghc) {
+  constexpr bool GHC = decltype(ghc)::value;
   // Round trip 2: the window's vector entries FIRST (they return first, and the workgroup's barrier waits for them only), then the row's
   // first batch -- before the row length is known: it lies inside the row's slot whatever the length -- the length, and the operands of the
   // row's tail (the row is the same for the 64 lanes: scalar loads, no vector registers).
   double2 x0 = make_double2(0.0, 0.0), x1 = x0;
   if (t0 < nslots) x0 = xv[min(wk0 + (t0 & (WIN_UNIT - 1)), G - 1)];
   if (t1 < nslots) x1 = xv[min(wk1 + (t1 & (WIN_UNIT - 1)), G - 1)];
-  request(0, live ? S10 : 0);
+  if (!BP) request(0, live ? S10 : 0);             // (BP: in flight since the top of the wavefront)
   const int rowc = live ? (roword ? ridx : row) : 0;         // index of this row in the per-row arrays
   const int n = live ? (n10[rowc] & N10_COUNT) : 0;
   const int tl_t = type[rowc];
@@ -374,13 +406,17 @@ struct WinPassArgs {
   const double2 *xv, *hst; double2 *gst; const double2 *qst; const double *q; const int *type; const double *scal; double *partials; double2 *rs_all, *rs_gh; const double *hsc; const double4 *pqrow;
   const int *grouplist; int ngroups, pbase; const double *stopflag; const int *gflags; int roword;
   int win_maxunits; hipStream_t stream;               // geometry: ngroups workgroups of WIN_ROWS wavefronts, the largest window of the build in LDS
+  bool byplace = false;                               // layout of the streams (Engine::streams_by_place): selects the BP instance
 };
 template <int MODE, bool STORE, bool PQ, int NSTEP = 2, int VAR = 0, class VT = double>
 inline void launch_win(const WinPassArgs &a) {
   const VT *values = [&] { if constexpr (std::is_same<VT, float>::value) return a.hess32; else return a.hess; }();
-  k_spmv_win<MODE, STORE, PQ, NSTEP, VAR, VT><<<a.ngroups, 64 * WIN_ROWS, static_cast<size_t>(a.win_maxunits) * WIN_UNIT * sizeof(double2), a.stream>>>(
-      a.N, a.G, a.S10, a.ff, a.sl10, values, a.n10, a.rows_sorted, a.win_k, a.win_cnt, a.xv, a.hst, a.gst, a.qst, a.q, a.type, a.scal, a.partials, a.rs_all, a.rs_gh, a.hsc, a.pqrow,
-      a.grouplist, a.ngroups, a.pbase, a.stopflag, a.gflags, a.roword);
+  auto go = [&](auto bp) {
+    k_spmv_win<MODE, STORE, PQ, NSTEP, VAR, VT, decltype(bp)::value><<<a.ngroups, 64 * WIN_ROWS, static_cast<size_t>(a.win_maxunits) * WIN_UNIT * sizeof(double2), a.stream>>>(
+        a.N, a.G, a.S10, a.ff, a.sl10, values, a.n10, a.rows_sorted, a.win_k, a.win_cnt, a.xv, a.hst, a.gst, a.qst, a.q, a.type, a.scal, a.partials, a.rs_all, a.rs_gh, a.hsc, a.pqrow,
+        a.grouplist, a.ngroups, a.pbase, a.stopflag, a.gflags, a.roword);
+  };
+  if (a.byplace) go(std::true_type{}); else go(std::false_type{});
 }
 // one wavefront per row, sixteen rows per workgroup: measured faster than a persistent grid-stride launch (1.10 vs 1.28 ms
 // per pass at 979,776 rows) -- many short waves overlap each other's load / gather / reduce phases (NOTES.md 3, K4/K5)
@@ -390,12 +426,13 @@ struct RowPassArgs {
   const double2 *xv, *hst; double2 *gst; const double2 *qst; const double *q; const int *type; const double *scal; double *partials;
   double2 *rs_all, *rs_gh; const double *hsc; const double4 *pqrow; int swz; const int *rowlist; int nrows, pbase; const double *stopflag;
   hipStream_t stream;
+  const int *rplace = nullptr;
   int nblocks() const { return nblk(rowlist ? nrows : N, SPMV_WPB); }
 };
 template <int MODE, bool STORE, bool PQ, int PIPE>
 inline void launch_row(const RowPassArgs &a) {
   k_spmv<MODE, STORE, PQ, PIPE><<<a.nblocks(), 64 * SPMV_WPB, 0, a.stream>>>(a.N, a.S10, a.ff, a.nb10, a.hess, a.n10, a.xv, a.hst, a.gst, a.qst, a.q, a.type, a.scal, a.partials, a.rs_all, a.rs_gh, a.hsc, a.pqrow, a.swz,
-                                                                            a.rowlist, a.nrows, a.pbase, a.stopflag);
+                                                                            a.rowlist, a.nrows, a.pbase, a.stopflag, a.rplace);
 }
 
 // the mean time [ms] of `reps` launches behind `warm` untimed ones (events ev[2], ev[3] of the engine; returns when the last launch is through)
