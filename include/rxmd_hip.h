@@ -243,6 +243,42 @@ long long rxmd_hip_get_bonds_device(rxmd_handle h, int flags, double bo_min, lon
 int rxmd_hip_bonds_vjp_device(rxmd_handle h, int flags, double bo_min, long long E, const double *grad_bo, const double *grad_bo3,
                               const double *grad_vec3, double *grad_pos3, void *stream);
 
+/* The 10 A pair graph -- the radius graph the engine builds on every step -- as coordinate (COO) arrays in DEVICE memory: the residents' rows of
+ * the 10 A list (nbplist; what ENbond and the QEq matrix walk), compacted on the device.  Every entry of a resident's row with |vec| <= r_cut is
+ * selected, |vec| being the norm of the vec3 this call returns (double, from the positions the engine holds, the partner as the list holds it).
+ * r_cut <= 0 selects EVERY entry of the list: the reference's own membership (dr^2 of the pair inside the taper cut-off, main.F90:458; in a skewed
+ * cell also its non-bonded mesh test), per-row counts equal to nbplist(0,:).  r_cut above the list's reach -- the taper cut-off: 10 A, 12.5 A on an
+ * engine created with pqeq_path -- is RXMD_E_ARG: the list does not hold those pairs.  Order: resident order (the order of rxmd_hip_get_atoms, and
+ * the caller's order after rxmd_hip_evaluate_device), within a resident the list's own entry order.  The compaction is a scan: stable, no atomics,
+ * two calls on one state return the same bits.  The graph is DIRECTED (a pair of residents appears once from each end) and a MULTIGRAPH: in a box
+ * with an edge shorter than twice r_cut the same dst appears once per periodic image within reach, each with its own shift.  src == dst with a
+ * non-zero shift (an atom and its own image) is legal output: it occurs once r_cut reaches a box edge.  The engine accepts any local box above the
+ * bond cut-off and its ghost shell holds ONE image per direction, as the reference's does: the list is the complete radius graph for r_cut up to
+ * the shortest perpendicular width of the box; a pair that needs an image two boxes away (r_cut above that width) is not in the list.
+ *   src[e], dst[e]  local indices of the owning resident and of the resident that owns the partner (a ghost partner is resolved to its owner as in
+ *                   rxmd_hip_get_bonds_device); single rank only.  With RXMD_PAIRS_GID in flags both are global ids instead (any vprocs)
+ *   shift3[3e..]    the integers n with vec = r[dst] - r[src] + n1 a1 + n2 a2 + n3 a3 for the engine-held (wrapped) resident positions:
+ *                   rint(H^-1 (r_ghost - r_owner)), zero for a resident partner; single rank only; NULL: not wanted
+ *   vec3[3e..]      r_partner - r_owner with the partner's coordinates as the engine holds them: the ghost is the right periodic image, so there is
+ *                   no minimum-image step, in any cell, and it does not depend on where in space the caller's positions were; NULL: not wanted
+ *   hval[e]         the off-diagonal QEq matrix value of that entry as the last list build stored it (qeq_initialize's hessian; PQEq: the
+ *                   core-core value): src, dst, hval are the QEq operator as a sparse COO matrix, its diagonal being the ffield's eta (not an edge).
+ *                   With the fp32 matrix stream in use (rxmd_hip_set_qeq_precision(32)): the rounded value, widened.  The list sweep forms the
+ *                   values whatever isQEq is (k_list10 does not look at it), so hval needs no restriction; NULL: not wanted
+ * All five are device pointers.  Returns E, the number of directed pairs selected (64-bit: a dense domain holds more than 2^31), or a negative
+ * RXMD_E_* code.  src = dst = NULL: count only (capacity and the other arrays ignored).  Otherwise src and dst go together (RXMD_E_ARG when one is
+ * missing) and hold `capacity` entries (shift3: 3 * capacity ints, vec3: 3 * capacity doubles); when capacity < E NOTHING is written and E is still
+ * returned, so the caller compares.  One host wait per call, for E.  Stream protocol of rxmd_hip_get_bonds_device: the engine's stream waits for
+ * what `stream` (NULL = the null stream) held at entry, `stream` waits for an event recorded behind the fill kernel.
+ * RXMD_E_STATE: there is no valid 10 A list -- no rxmd_hip_qeq / rxmd_hip_force (or evaluate / step) yet, or set_atoms / set_lattice /
+ * set_qeq_precision since.  RXMD_E_ARG (checked first): unknown bits in flags, a negative capacity, a non-finite r_cut, r_cut beyond the reach,
+ * local indices (no RXMD_PAIRS_GID) or shift3 on an engine with vprocs other than 1 1 1.  Global ids with vec3 / hval work on any rank grid and on
+ * engines created with pqeq_path.  The call reads the list and changes nothing any other entry point returns; an engine that never asks allocates
+ * and launches nothing for it.  No counterpart in the reference. */
+#define RXMD_PAIRS_GID 1   /* src/dst are global ids instead of local resident indices */
+long long rxmd_hip_get_pairs_device(rxmd_handle h, int flags, double r_cut, long long capacity, long long *src, long long *dst, int *shift3,
+                                    double *vec3, double *hval, void *stream);
+
 /* ---- introspection for tests, roofline accounting and the timers table (main.F90:135-182) ---- */
 typedef struct rxmd_stats {
   int natoms, nghost_qeq, nghost_force; /* copyptr(6)-NATOMS after the QEq / FORCE ghost builds */

@@ -195,6 +195,10 @@ void Engine::declare_buffers() {
   for (double **t : {&bv_c1, &bv_c2, &bv_c3, &bv_t}) b.add(*t, G_BVJP, Dim::Cap, 1, 0, P, never);
   b.add(bv_cc, G_BVJP, Dim::NB, 1, 0, P, never);
   for (int a = 0; a < 3; ++a) b.add(bv_g[a], G_BVJP, Dim::NB, 1, 0, P, never);
+  // rxmd_hip_get_pairs_device (pair_graph.hip): selected entries per resident row of the 10 A list and their exclusive sum, 64-bit (+ 1: the total);
+  // first use allocates them at the rows10 of that day (Engine::select_pairs re-allocates when the rows have grown); an engine that never asks has neither
+  b.add(pg_cnt, G_PGRAPH, Dim::Rows10, 1, 1, P, never);
+  b.add(pg_off, G_PGRAPH, Dim::Rows10, 1, 1, P, never);
 }
 
 size_t Buffers::count(const Buf &b, const Engine &e) const {

@@ -420,6 +420,13 @@ long long rxmd_hip_get_bonds_device(rxmd_handle h, int flags, double bo_min, lon
   return rc < 0 ? rc : n;
 }
 
+long long rxmd_hip_get_pairs_device(rxmd_handle h, int flags, double r_cut, long long capacity, long long *src, long long *dst, int *shift3, double *vec3,
+                                    double *hval, void *stream) {
+  long long n = 0;
+  const int rc = guarded(h, [&](Engine &e) { n = e.pairs_device(flags, r_cut, capacity, src, dst, shift3, vec3, hval, static_cast<hipStream_t>(stream)); });
+  return rc < 0 ? rc : n;
+}
+
 int rxmd_hip_bonds_vjp_device(rxmd_handle h, int flags, double bo_min, long long E, const double *grad_bo, const double *grad_bo3,
                               const double *grad_vec3, double *grad_pos3, void *stream) {
   return guarded(h, [&](Engine &e) { e.bonds_vjp_device(flags, bo_min, E, grad_bo, grad_bo3, grad_vec3, grad_pos3, static_cast<hipStream_t>(stream)); });

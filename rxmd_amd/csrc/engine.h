@@ -191,7 +191,7 @@ enum class Dim : unsigned char { Fixed, NB, Rows10, List10, Cap };   // what a b
 enum class Refill : unsigned char { Never, Whole, Ghosts };          // RXMD_POISON_ALLOC refill before a rebuild: none, the whole buffer, elements [N, NB)
 enum class Space : unsigned char { Device, Pinned, PinnedCoherent };
 // re-allocation groups.  Those before G_ON_DEMAND exist from set-up on (Buffers::alloc_setup); the others are allocated when first needed
-enum { G_SETUP, G_BOND, G_WIN, G_CELLSTART, G_LIST10, G_PARTIALS, G_ON_DEMAND, G_CUBTMP = G_ON_DEMAND, G_FFBLOB, G_PQBLOB, G_E4B, G_SEG, G_SEG_PINNED, G_XBUF, G_DH_SERVE, G_BGRAPH, G_BVJP, G_COUNT };
+enum { G_SETUP, G_BOND, G_WIN, G_CELLSTART, G_LIST10, G_PARTIALS, G_ON_DEMAND, G_CUBTMP = G_ON_DEMAND, G_FFBLOB, G_PQBLOB, G_E4B, G_SEG, G_SEG_PINNED, G_XBUF, G_DH_SERVE, G_BGRAPH, G_BVJP, G_PGRAPH, G_COUNT };
 enum : unsigned { BUF_PQEQ = 1u, BUF_RESIDENT = 2u, BUF_QEQ_F32 = 4u };   // exists only with PQEq ; resident state that grow_capacity carries over ; exists only while the fp32 matrix stream is requested (set_qeq_precision)
 struct Buf { void **pp; size_t elem; int group; Dim dim; size_t mul, add_; Fill fill; Refill refill; unsigned flags; Space space; size_t bytes; };   // bytes: what was allocated (0: nothing of ours)
 struct Buffers {
@@ -233,6 +233,7 @@ struct StreamSwap {                                   // the engine's stream aga
 };
 
 struct ScaleArgs;
+struct PairList;                         // what the kernels of pair_graph.hip need to walk a row of the 10 A list
 struct WinPassArgs; struct RowPassArgs;   // the operands of the two matrix-pass kernels (spmv_kernels.h)
 struct Engine {
   const Options opt = Options::from_env();   // the environment switches of this engine (options.def), read once at create
@@ -388,6 +389,14 @@ struct Engine {
   // ccbnd term), bv_cc and bv_g (per atom, ghost slots included); allocated on first use at the capacities of the day (bv_nb: the NB they were sized for)
   void bonds_vjp_device(int flags, double bo_min, long long E, const double *grad_bo_d, const double *grad_bo3_d, const double *grad_vec3_d, double *grad_pos3_d, hipStream_t user);
   double *bv_c1 = nullptr, *bv_c2 = nullptr, *bv_c3 = nullptr, *bv_t = nullptr, *bv_cc = nullptr, *bv_g[3] = {nullptr, nullptr, nullptr}; int bv_nb = 0;
+  // rxmd_hip_get_pairs_device (pair_graph.hip): the residents' rows of the 10 A list as coordinate (COO) arrays in DEVICE memory, entries with
+  // |vec| <= r_cut (r_cut <= 0: all) in resident order and list order -- count per row, 64-bit exclusive sum, fill.  src = dst = nullptr: count only.
+  // Returns the number selected; nothing is written when capacity is smaller.  pg_cnt / pg_off: its scratch, one 64-bit word per row + 1, allocated on
+  // first use at the rows10 of the day (pg_rows) and again when the rows have grown
+  long long pairs_device(int flags, double r_cut, long long capacity, long long *src_d, long long *dst_d, int *shift3_d, double *vec3_d, double *hval_d, hipStream_t user);
+  long long select_pairs(double r_cut);            // pg_cnt / pg_off for this cut-off -> the number selected (the one host wait of the call)
+  PairList pair_list(double r_cut) const;
+  long long *pg_cnt = nullptr, *pg_off = nullptr; int pg_rows = 0;
   void build_ghosts_and_lists(bool qeq_prepass = false);   // COPYATOMS(MODE_COPY) + LINKEDLIST + NEIGHBORLIST + 10 A list/hessian, once per step
   void qeq_start_vectors();        // qs, qt, hs, ht of qeq.F90:36-63 and their cell-sorted copy (before the list sweep that uses them)
   int *rows_int = nullptr, *rows_bnd = nullptr; int n_bnd = 0; bool rows_split_pending = false;   // interior / boundary rows (multi-rank)

@@ -14,6 +14,7 @@ from ._lib import RxmdConfig, RxmdStats
 
 PE_NAMES = ["Esystem", "Ebond", "Elp", "Eover", "Eunder", "Eval", "Epen", "Ecoa", "Etors", "Econj", "Ehbond", "Evdwaals", "Ecoulomb", "Echarge"]
 BONDS_GID = 1      # RXMD_BONDS_GID of include/rxmd_hip.h
+PAIRS_GID = 1      # RXMD_PAIRS_GID
 
 
 class RxmdError(RuntimeError):
@@ -268,6 +269,17 @@ class RxmdEngine:
         written); float64 grad_pos[natoms][3] receives dL/dpos in the order of atoms() (overwritten)"""
         p = [C.c_void_p(int(a) or None) for a in (grad_bo_ptr, grad_bo3_ptr, grad_vec_ptr, grad_pos_ptr)]
         self._chk(self.L.rxmd_hip_bonds_vjp_device(self.h, BONDS_GID if as_gid else 0, float(bo_min), int(E), p[0], p[1], p[2], p[3], C.c_void_p(int(stream) or None)))
+
+    def pairs_device(self, capacity, src_ptr, dst_ptr, shift_ptr=0, vec_ptr=0, h_ptr=0, r_cut=0.0, as_gid=False, stream=0):
+        """the 10 A pair graph of the last list build as coordinate arrays in device memory, given as integer addresses (include/rxmd_hip.h:
+        rxmd_hip_get_pairs_device): int64 src[capacity], dst[capacity], optional int32 shift[capacity][3] (periodic image of dst), float64
+        vec[capacity][3] (r_dst - r_src through that image) and float64 h[capacity] (the QEq matrix value of the entry).  Every list entry with
+        |vec| <= r_cut (r_cut <= 0: the whole list; above the taper cut-off: RxmdError -1), in the order of atoms() and list order within an atom;
+        directed, one edge per image.  src / dst are local indices, global ids with as_gid.  src_ptr = dst_ptr = 0: count only.
+        -> E, the number of directed pairs selected; nothing is written when capacity < E"""
+        p = [C.c_void_p(int(a) or None) for a in (src_ptr, dst_ptr, shift_ptr, vec_ptr, h_ptr)]
+        return self._chk(self.L.rxmd_hip_get_pairs_device(self.h, PAIRS_GID if as_gid else 0, float(r_cut), int(capacity), p[0], p[1], p[2], p[3], p[4],
+                                                          C.c_void_p(int(stream) or None)))
 
     # ---- introspection ----
     def stats(self):

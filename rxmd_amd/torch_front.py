@@ -11,6 +11,8 @@ a bias potential, an integrator or a correction model written in torch composes 
     g = model.bond_graph(bo_min=0.3)    # dict(edge_index [2, E], bond_order [E], edge_vec [E, 3]) of the last evaluate, device tensors
 
     b = model.bond_orders(pos, bo_min=0.3)   # the same graph of a fresh evaluate, DIFFERENTIABLE in pos (with energy, forces, charges)
+    p = model.pair_graph(6.0, pos=pos)       # the radius graph of the last evaluate: dict(edge_index [2, E], shifts [E, 3], vec [E, 3]), vec
+                                             # differentiable in pos by plain autograd; values=True adds h [E], the QEq matrix value per edge
 
 The bond-order graph (`bond_graph`, or `evaluate(pos, bond_graph=bo_min)`) is what FORCE left in the engine's bond tables, compacted on the device
 (RxmdEngine.bonds_device -> rxmd_hip_get_bonds_device).  From those two calls it is NOT differentiable: bond orders and bond vectors come out as
@@ -176,6 +178,61 @@ class ReaxFF:
         out = dict(edge_index=edge, bond_order=bo, edge_vec=vec)
         if components:
             out["bond_order_parts"] = parts
+        return out
+
+    def cell(self):
+        """the lattice vectors of the engine's box as the ROWS of a [3, 3] float64 tensor on the model's device (a constant)"""
+        la, lb, lc, al, be, ga = self.engine.lattice
+        ca, cb, cg, sg = (np.cos(np.radians(al)), np.cos(np.radians(be)), np.cos(np.radians(ga)), np.sin(np.radians(ga)))
+        h2 = lc * np.sqrt(1.0 - ca * ca - cb * cb - cg * cg + 2.0 * ca * cb * cg) / sg
+        rows = [[la, 0.0, 0.0], [lb * cg, lb * sg, 0.0], [lc * cb, lc * (ca - cb * cg) / sg, h2]]      # GetBoxParams, init.F90:610-633
+        return torch.tensor(rows, dtype=torch.float64, device=self.device)
+
+    def pair_graph(self, r_cut, pos=None, values=False, cell=None):
+        """The radius graph of the last evaluate / energy call -- the engine's own 10 A list, every pair with |vec| <= r_cut through every periodic
+        image within reach (r_cut <= 0: the whole list; above the taper cut-off, 10 A: RxmdError -1; RxmdError -7 before the first evaluate or
+        after set_lattice) -- as fresh tensors on the model's device, produced on torch's current stream:
+            edge_index [2, E] int64    (src, dst) in the caller's atom order; directed, and one edge per image: in a small box a pair repeats
+            shifts     [E, 3] int64    the image n of dst: vec = pos[dst] - pos[src] + n @ cell (cell: lattice vectors as rows)
+            vec        [E, 3] float64  r_dst - r_src through that image
+            h          [E]    float64  with values=True: the QEq matrix value of the pair (edge_index + h = the off-diagonal part of the QEq operator
+                                       as a COO matrix; its diagonal is the ffield's eta)
+        Edges are ordered by src, then by the engine's list order.  Count, allocate exactly, fill: two device passes, one host wait each.
+        Without pos: shifts refer to the engine's wrapped positions and every tensor is a constant.  With pos = the tensor of the last evaluate
+        (anywhere in space, possibly requiring grad): shifts are re-expressed for those coordinates -- n' = rint((vec - (pos[dst] - pos[src])) cell^-1),
+        an exact integer recovery -- and vec is RETURNED AS pos[dst] - pos[src] + n' @ cell, computed in torch: differentiable in pos, and in `cell`
+        when that is given as a [3, 3] tensor (default: the engine's lattice, a constant), by plain autograd.  edge_index, shifts and h are constants:
+        which pairs are selected is not differentiated, and h carries no gradient (no dH/dr)."""
+        if isinstance(r_cut, (bool, np.bool_)) or not isinstance(r_cut, (int, float, np.integer, np.floating)):
+            raise ValueError("r_cut must be a real number, got %s" % type(r_cut).__name__)
+        r_cut = float(r_cut)
+        if not isinstance(values, (bool, np.bool_)):
+            raise ValueError("values must be a bool, got %s" % type(values).__name__)
+        if pos is not None:
+            _check_pos(pos, self.natoms, self.device)
+        if cell is not None and (not isinstance(cell, torch.Tensor) or cell.dtype != torch.float64 or cell.shape != (3, 3) or cell.device != self.device):
+            raise ValueError("cell must be a float64 tensor of shape [3, 3] on %s (lattice vectors as rows)" % self.device)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            E = self.engine.pairs_device(0, 0, 0, r_cut=r_cut, stream=stream)
+            kw = dict(device=self.device)
+            edge = torch.empty((2, E), dtype=torch.int64, **kw)
+            shift32 = torch.empty((E, 3), dtype=torch.int32, **kw)
+            vec = torch.empty((E, 3), dtype=torch.float64, **kw)
+            h = torch.empty(E, dtype=torch.float64, **kw) if values else None
+            if E > 0:
+                got = self.engine.pairs_device(E, edge[0].data_ptr(), edge[1].data_ptr(), shift_ptr=shift32.data_ptr(), vec_ptr=vec.data_ptr(),
+                                               h_ptr=h.data_ptr() if values else 0, r_cut=r_cut, stream=stream)
+                assert got == E, "the 10 A list changed between the count and the fill"
+            shifts = shift32.to(torch.int64)
+            if pos is not None:
+                c = self.cell() if cell is None else cell
+                d = pos[edge[1]] - pos[edge[0]]
+                shifts = torch.round((vec - d.detach()) @ torch.linalg.inv(c.detach())).to(torch.int64)
+                vec = d + shifts.to(torch.float64) @ c
+        out = dict(edge_index=edge, shifts=shifts, vec=vec)
+        if values:
+            out["h"] = h
         return out
 
     def bond_orders(self, pos, bo_min=0.0, components=False, q0=None):
