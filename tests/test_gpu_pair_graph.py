@@ -12,6 +12,9 @@ Bounds, and where they come from:
   * shift3 and the multiset of (src, dst, shift): exact.  The test first asserts that no brute-force distance lies within 1e-8 A of r_cut, so the
     roundings above cannot move an edge across the cut-off.
   * per-row sums of hval against tap 7 / tap 108: rtol 1e-12, the tolerance of test_gpu_parity.py:81 (same numbers, another summation order).
+  * hval entry by entry against numpy on the oracle's table (qeq_table, hval_of_r2, check_hval_entries): 8 eps |h|, three rounded operations on
+    either side of (1 - t) T[itb] + t T[itb + 1]; the reference is taken in the four forms a compiler's FMA contraction of its two inner products
+    leaves, one form must hold all entries of a system (all ranks), and at most 2 entries per system may match at the float next to float32(|vec|^2).  Derived in check_hval_entries.  fp32 stream: exact.
   * torch, d/dpos of sum |vec|^2 against 2 (scatter(vec, dst) - scatter(vec, src)): both sides sum the same <= ~300 terms of magnitude <= 2 r_cut
     per atom in different orders: <= 300 eps x 300 x 13 A = 2.6e-10; asserted at 1e-9.
   * the QEq stationarity chi + H q = const from the exported matrix: no number fixed in advance; the engine's charges are allowed ten times the
@@ -213,6 +216,135 @@ def test_whole_list_counts_and_row_sums_equal_the_taps(case):
     print(case, "E", E, "row sums vs tap 7: max rel %.2e, vs tap 108: max rel %.2e" % (np.abs(rows / t7 - 1).max(), np.abs(rows / t108 - 1).max()))
     assert np.allclose(rows, t7, rtol=1e-12, atol=0.0) and np.allclose(rows, t108, rtol=1e-12, atol=0.0)
     assert (np.linalg.norm(vec, axis=1) <= 10.0 * (1 + 1e-12)).all()
+    e.close()
+
+
+# ---- 2b. hval entry by entry ------------------------------------------------------------------------------------------------------------------
+EPS = np.finfo(np.float64).eps
+RCTAP = 10.0                                       # the taper cut-off of plain QEq (init.F90:28-34)
+
+
+def qeq_table(o, ff):
+    """what an entry of the QEq matrix is looked up in: the oracle's TBL_Eclmb_QEq (Oracle.table(4): row inxn - 1, column i - 1 of the node i = 1..NTABLE)
+    and the row of a pair of types, inxn2, read from the bond section of the ffield as rxmd_oracle.c:186-206 reads it (bond `ih` of the file serves
+    the two types its line starts with).  The oracle hands out the table only; UDR, UDRi and rctap2 are formed as it forms them (rxmd_oracle.c:316,1894)."""
+    T = o.table(4)
+    lines = open(ff).read().split("\n")
+    npar = int(lines[1].split()[0])
+    nso = int(lines[2 + npar].split()[0])
+    at = 2 + npar + 4 + 4 * nso                    # the line with the number of bonds; one more header line, then two lines per bond
+    nboty = int(lines[at].split()[0])
+    assert nboty == T.shape[0]
+    inxn2 = np.zeros((nso + 1, nso + 1), dtype=np.int64)
+    for ih in range(1, nboty + 1):
+        ta, tb = int(lines[at + 2 * ih][0:3]), int(lines[at + 2 * ih][3:6])
+        inxn2[ta, tb] = inxn2[tb, ta] = ih
+    rctap2 = RCTAP * RCTAP
+    UDR = rctap2 / T.shape[1]
+    return dict(T=T, inxn2=inxn2, UDR=UDR, UDRi=1.0 / UDR, rctap2=rctap2)
+
+
+FORMS = ((False, False), (True, False), (False, True), (True, True))
+
+
+def _two_product(a, b):
+    """a b = p + e exactly, p the rounded product (Dekker; Veltkamp's split at 2^27 + 1)"""
+    split = lambda x: (lambda c: (c - (c - x), x - (c - (c - x))))(134217729.0 * x)
+    p = a * b
+    (ah, al), (bh, bl) = split(a), split(b)
+    return p, al * bl - (((p - ah * bh) - al * bh) - ah * bl)
+
+
+def hval_of_r2(tab, r2f, inxn, form=(False, False)):
+    """qeq_initialize's entry for REAL(4) squared distances r2f (qeq.F90:191,222-240 as rxmd_oracle.c:659-669 restates it), in numpy doubles:
+    a = r2 - itb UDR, t = a UDRi, h = (1 - t) T[itb] + t T[itb + 1].  form = (f1, f2): which of the two products a compiler has contracted into the
+    subtraction behind it (an FMA: one rounding instead of two) -- f1: r2 - itb UDR, f2: 1 - a UDRi.  The contracted results are formed here from
+    Dekker's exact product: r2 - (rounded product) is exact (the two lie within a factor of two), 1 - (rounded product) is followed by its exact
+    rounding error (TwoSum), so one rounding remains in either."""
+    r2 = r2f.astype(np.float64)
+    itb = (r2 * tab["UDRi"]).astype(np.int64)
+    p, pe = _two_product(itb.astype(np.float64), np.float64(tab["UDR"]))
+    a = ((r2 - p) - pe) if form[0] else (r2 - p)
+    t, te = _two_product(a, np.float64(tab["UDRi"]))
+    one_t = 1.0 - t
+    if form[1]:
+        bb = one_t - 1.0
+        one_t = one_t + (((1.0 - (one_t - bb)) + (-t - bb)) - te)
+    inside = (r2 < tab["rctap2"]) & (inxn != 0)
+    assert (itb[inside] >= 1).all() and (itb[inside] < tab["T"].shape[1]).all()
+    row, col = np.where(inside, inxn - 1, 0), np.where(inside, itb, 1)
+    h = one_t * tab["T"][row, col - 1] + t * tab["T"][row, col]
+    return np.where(inside, h, 0.0)
+
+
+def check_hval_entries(vec, hv, ti, tj, tab, label, f32=False, form=None):
+    """every exported value against the table look-up at float32(|vec|^2), |vec|^2 formed from the exported vec3.
+    Bound 8 eps |h|: the kernel and this reference both interpolate as (1 - t) T[itb] + t T[itb + 1] (lists.hip, k_list10), three rounded operations on
+    either side, and the two terms have one sign.  With the fp32 stream the reference is float64(float32(h)), exact.
+    That count of roundings holds only when both sides round the SAME intermediate results, and in two places of this expression it matters far above
+    the bound whether a product is rounded before the subtraction behind it: itb UDR ~ r2 carries eps r2 / 2, which UDRi turns into up to 2,500 eps in t
+    and the slope of the table into tens of eps |h| (11 measured against the uncontracted form at 9.46 A); and towards the end of the taper, where
+    T[itb + 1] -> 0 and t -> 1, the rounding of t is eps / 2 against 1 - t (9 eps |h| measured at r^2 = 99.9997).  hipcc contracts such products into
+    FMAs; a compiler may also leave them.  So the reference is evaluated in the four forms of the same expression (hval_of_r2: each of the two
+    products contracted or not), and ONE form must hold every entry of a system to 8 eps |h|: with form=None the form with the fewest misses, then
+    the smallest largest error, is taken, printed and returned; a caller with several calls on one system (one per rank: one kernel build) hands
+    the form of the first call to the others.  (Contracting the last line as well moves h by less than 2 eps.)
+    The kernel may contract d0^2 + d1^2 + d2^2 into FMAs too: an entry whose double |vec|^2 lies within 4 ulp of the midpoint between two floats may
+    match the look-up at either of them; at most 2 entries per SYSTEM may (expected ~1e-3 of one): asserted here per call, and by a caller with
+    several calls on the sum of the returned counts.
+    -> (largest error in units of eps |h|, entries that used the escape, the form)"""
+    r2d = (vec * vec).sum(axis=1)
+    r2f = r2d.astype(np.float32)
+    inxn = tab["inxn2"][ti, tj]
+    held = np.ones(len(hv), dtype=bool)
+
+    def ref_at(r2f_, inxn_, form):
+        h = hval_of_r2(tab, r2f_, inxn_, form)
+        return h.astype(np.float32).astype(np.float64) if f32 else h
+
+    def misses(form):
+        ref = ref_at(r2f, inxn, form)
+        err = np.abs(hv - ref)
+        return ref, err, held & (err > (0.0 if f32 else 8 * EPS * np.abs(ref)))
+
+    def rank(f):                                   # fewest entries beyond the bound, then the smallest largest error
+        ref_, err_, bad_ = misses(f)
+        nz_ = held & (ref_ != 0.0)
+        return int(bad_.sum()), float((err_[nz_] / np.abs(ref_[nz_])).max()) if nz_.any() else 0.0
+
+    if form is None:
+        form = min(FORMS, key=rank)
+    ref, err, bad = misses(form)
+    escapes = 0
+    for k in np.nonzero(bad)[0]:
+        ok = False
+        for nb in (np.nextafter(r2f[k], np.float32(-np.inf)), np.nextafter(r2f[k], np.float32(np.inf))):
+            mid = 0.5 * (float(r2f[k]) + float(nb))
+            if abs(r2d[k] - mid) <= 4 * np.spacing(r2d[k]):
+                alt = ref_at(np.array([nb], dtype=np.float32), inxn[k:k + 1], form)[0]
+                if abs(hv[k] - alt) <= (0.0 if f32 else 8 * EPS * abs(alt)):
+                    ok = True; err[k] = abs(hv[k] - alt); ref[k] = alt
+        assert ok, "%s: entry %d, |vec|^2 %.17g: hval %.17g, the table gives %.17g (form %s, %d entries beyond the bound)" % (label, k, r2d[k], hv[k], ref[k], form, int(bad.sum()))
+        escapes += 1
+    nz = held & (ref != 0.0)
+    worst = (err[nz] / np.abs(ref[nz])).max() / EPS if nz.any() else 0.0
+    print("%s: %d entries held, %d of them zero, max |hval - table| %.2f eps |h|%s, products contracted (r2 - itb UDR, 1 - a UDRi): %s, "
+          "entries matched at the neighbouring float %d" % (label, int(held.sum()), int((held & (ref == 0.0)).sum()), worst, " (fp32 stream: exact)" if f32 else "", form, escapes))
+    assert (err[held & (ref == 0.0)] == 0.0).all()
+    assert escapes <= 2
+    return worst, escapes, form
+
+
+@pytest.mark.parametrize("case", ["rdx168", "rdx-shaken"])
+def test_hval_entry_by_entry_equals_the_table_lookup(case):
+    o = ol.oracle(case, **KW5) if case in ol.SYSTEMS else _oracle(case, (1, 1, 1), **KW5)
+    ff = ol.build(case)[0] if case in ol.SYSTEMS else oa.make_system(case)[0]
+    tab = qeq_table(o, ff)
+    e = _make(case); e.QEq(); e.FORCE()
+    typ = e.atoms()["type"]
+    E, s, d, sh, vec, hv = device_coo(e, 0.0)
+    assert E == e.stats()["nnz10"] and (hv != 0.0).any()
+    check_hval_entries(vec, hv, typ[s], typ[d], tab, case)
     e.close()
 
 
