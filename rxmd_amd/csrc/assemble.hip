@@ -22,8 +22,6 @@
 
 namespace rxmd {
 
-static inline int nblk(long long n, int b) { return n > 0 ? static_cast<int>((n + b - 1) / b) : 1; }   // an empty rank still launches (kernels guard their range)
-
 // Bond tables are compact (CSR, engine.h): bond o = boff[i] + s, its mirror image -- the same bond in the partner's list -- is brev[o].
 __global__ void __launch_bounds__(256) k_cd_gather(int G, const int *__restrict__ boff, const int *__restrict__ brev,
                                                     const double *__restrict__ cds, const double *__restrict__ cdn, double *__restrict__ cd) {

@@ -28,8 +28,6 @@
 
 namespace rxmd {
 
-static inline int nblk(long long n, int b) { return n > 0 ? static_cast<int>((n + b - 1) / b) : 1; }
-
 // a1..a3 of table entry o from the edge-ordered gradients (zero for an entry the selection left out and for every ghost row)
 __device__ inline void bvjp_coef(int o, int nres, const int *__restrict__ flag, const int *__restrict__ off, const double *__restrict__ gbo,
                                  const double *__restrict__ gbo3, double &a1, double &a2, double &a3) {
@@ -114,14 +112,11 @@ void Engine::bonds_vjp_device(int flags, double bo_min, long long E, const doubl
   if (!atoms_set || !lists_valid) throw EngineError(RXMD_E_STATE, "no bond lists: call rxmd_hip_force first");
   const long long count = select_bonds(bo_min);      // the host wait of the call; bg_flag / bg_off now belong to this state and threshold
   if (count != E) throw EngineError(RXMD_E_ARG, "bonds_vjp_device: E = " + std::to_string(E) + ", but get_bonds_device selects " + std::to_string(count) + " edges for these flags and bo_min");
-  if (!ev_io_in) { RX_HIP(hipEventCreateWithFlags(&ev_io_in, hipEventDisableTiming)); RX_HIP(hipEventCreateWithFlags(&ev_io_out, hipEventDisableTiming)); }
   if (count > 0 && (!bv_c1 || bufs.cap[G_BVJP] < bcap || bv_nb != NB)) {   // first use, or the bond tables or the atom capacity have grown since
-    sync_stream();                                   // (the kernels of an earlier call may still read the old blocks)
-    bufs.free_group(G_BVJP); bufs.alloc_group(*this, G_BVJP, bcap);
+    regrow_group(G_BVJP, bcap);                      // (the kernels of an earlier call may still read the old blocks)
     bv_nb = NB;
   }
-  RX_HIP(hipEventRecord(ev_io_in, user));            // the caller's stream produced the gradients and may still hold work on grad_pos3
-  RX_HIP(hipStreamWaitEvent(stream, ev_io_in, 0));
+  UserStream io(this, user);                         // the caller's stream produced the gradients and may still hold work on grad_pos3
   if (count == 0) RX_HIP(hipMemsetAsync(grad_pos3_d, 0, sizeof(double) * 3 * static_cast<size_t>(N), stream));   // nothing selected: the gradient of nothing
   else {
     const int nres = nbonds_res;
@@ -133,8 +128,7 @@ void Engine::bonds_vjp_device(int flags, double bo_min, long long E, const doubl
     fold_ghost_forces(bv_g[0], bv_g[1], bv_g[2]);
     k_bvjp_egress<<<nblk(N, 256), 256, 0, stream>>>(N, bv_g[0], bv_g[1], bv_g[2], grad_pos3_d);
   }
-  RX_HIP(hipEventRecord(ev_io_out, stream));
-  RX_HIP(hipStreamWaitEvent(user, ev_io_out, 0));
+  io.end();
 }
 
 }  // namespace rxmd

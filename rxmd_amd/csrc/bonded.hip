@@ -24,8 +24,6 @@
 
 namespace rxmd {
 
-static inline int nblk(long long n, int b) { return n > 0 ? static_cast<int>((n + b - 1) / b) : 1; }   // an empty rank still launches (kernels guard their range)
-
 static constexpr double MINBO0 = 1e-4, cutof2_esub = 1e-4;                                        // module.F90:61-62
 static constexpr double MAXANGLE = 0.999999999999, MINANGLE = -0.999999999999, NSMALL = 1e-10;   // module.F90:85-87
 static constexpr double PI_ = 3.14159265358979;                                                  // module.F90:90
@@ -1360,8 +1358,10 @@ void Engine::bonded_energies() {
                                           cds, frc[0], frc[1], frc[2], pe_d);
   RX_HIP(hipGetLastError());                       // 70 KB of dynamic LDS: a refused launch must not pass for "no valence angles"
   kt3.end();
+  const DevBox hb = dev_box(box);
   BoxImg bx;
-  for (int a = 0; a < 3; ++a) { for (int c = 0; c < 3; ++c) { bx.H[3 * a + c] = box.H[a][c]; bx.Hi[3 * a + c] = box.Hi[a][c]; } bx.L[a] = box.lat[a]; }
+  for (int k = 0; k < 9; ++k) { bx.H[k] = hb.H[k]; bx.Hi[k] = hb.Hi[k]; }
+  for (int a = 0; a < 3; ++a) bx.L[a] = box.lat[a];
   bx.ortho = grid.ortho; bx.probe = 0;
   bx.probe = static_cast<int>(opt.e4b_probe);       // (experiments build only: 0 otherwise)
   // four atoms per wavefront when every bond list of this step fits 15 slots (h_err[2] = the largest list if longer than 8, read with the error word

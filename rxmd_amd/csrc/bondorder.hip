@@ -12,8 +12,6 @@
 
 namespace rxmd {
 
-static inline int nblk(long long n, int b) { return n > 0 ? static_cast<int>((n + b - 1) / b) : 1; }   // an empty rank still launches (kernels guard their range)
-
 __global__ void __launch_bounds__(256) k_bo_prime(int nbonds, DevFF ff, const int *__restrict__ bown, const int *__restrict__ nbr, const unsigned char *__restrict__ btype,
                                                    const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z, const int *__restrict__ type,
                                                    double *__restrict__ bo0, double *__restrict__ bo2, double *__restrict__ bo3,

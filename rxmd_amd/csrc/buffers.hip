@@ -62,7 +62,6 @@ void *pinned_alloc(size_t bytes, bool coherent_mapped) {
 void pinned_free(void *p) { if (p) (void)hipHostFree(p); }
 
 // ---- the table ------------------------------------------------------------------------------------------------------------------------
-constexpr size_t H_ERR_INTS = 32;        // 16 ints of the device error words + 16 (h_cnt) for the counts the host waits for
 constexpr size_t H_SEG_INTS = 32;        // totals of the 26-segment ghost build
 constexpr size_t H_PUB_WORDS = 32;       // words published through pinned memory (sequence number << 32 | value, pinned_wait)
 

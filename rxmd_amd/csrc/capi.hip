@@ -41,6 +41,43 @@ static int guarded(rxmd_handle h, F &&f) {
   }
 }
 
+// the count f returns, or the (negative) code of what it threw
+template <class F>
+static auto count_or_error(rxmd_handle h, F &&f) -> decltype(f(*h->e)) {
+  decltype(f(*h->e)) n = 0;
+  const int rc = guarded(h, [&](Engine &e) { n = f(e); });
+  return rc < 0 ? rc : n;
+}
+
+// the three component arrays of the device <-> rows [n][3] of the host
+static void pull3(double *const src[3], int n, double *dst) {
+  std::vector<double> tmp(n);
+  for (int a = 0; a < 3; ++a) {
+    RX_HIP(hipMemcpy(tmp.data(), src[a], sizeof(double) * n, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) dst[3 * static_cast<size_t>(i) + a] = tmp[i];
+  }
+}
+static void push3(const double *src, int n, double *const dst[3]) {
+  std::vector<double> tmp(n);
+  for (int a = 0; a < 3; ++a) {
+    for (int i = 0; i < n; ++i) tmp[i] = src[3 * static_cast<size_t>(i) + a];
+    RX_HIP(hipMemcpy(dst[a], tmp.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+  }
+}
+// n elements of an integer device array as doubles (mask: the bits that count)
+template <class T>
+static void pull_as_double(const T *src, int n, double *out, T mask = static_cast<T>(-1)) {
+  std::vector<T> t(n);
+  RX_HIP(hipMemcpy(t.data(), src, sizeof(T) * n, hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; ++i) out[i] = static_cast<double>(t[i] & mask);
+}
+// table `which` (0..4) of the force field, 1-based with NTABLE + 2 nodes per row, as dense rows [nboty][NTABLE]
+static void dense_table(const rxmd::ForceField &ff, int which, double *out) {
+  const std::vector<double> *src[5] = {&ff.tblEvdw, &ff.tbldEvdw, &ff.tblEclmb, &ff.tbldEclmb, &ff.tblQEq};
+  for (int r = 1; r <= ff.nboty; ++r)
+    for (int i = 1; i <= rxmd::NTABLE; ++i) out[static_cast<size_t>(r - 1) * rxmd::NTABLE + (i - 1)] = (*src[which])[static_cast<size_t>(r) * (rxmd::NTABLE + 2) + i];
+}
+
 extern "C" {
 
 void rxmd_hip_default_config(rxmd_config *c) {
@@ -89,33 +126,23 @@ int rxmd_hip_set_atoms_rxff(rxmd_handle h, int natoms, const double *rec10) {
 }
 
 int rxmd_hip_get_atoms_rxff(rxmd_handle h, double *rec10, int capacity) {
-  int n = 0;
-  const int rc = guarded(h, [&](Engine &e) { n = e.get_atoms_rxff(rec10, capacity); });
-  return rc < 0 ? rc : n;
+  return count_or_error(h, [&](Engine &e) { return e.get_atoms_rxff(rec10, capacity); });
 }
 
 int rxmd_hip_get_atoms(rxmd_handle h, int capacity, long long *gid, int *type, double *pos, double *v, double *f, double *q) {
-  int n = 0;
-  const int rc = guarded(h, [&](Engine &e) {
+  return count_or_error(h, [&](Engine &e) {
     if (!e.atoms_set) throw EngineError(RXMD_E_STATE, "atoms were never set");
-    n = e.N;
+    const int n = e.N;
     if (capacity < n) throw EngineError(RXMD_E_ARG, "capacity smaller than natoms");
     RX_HIP(hipStreamSynchronize(e.stream));
     if (gid) RX_HIP(hipMemcpy(gid, e.gid, sizeof(long long) * n, hipMemcpyDeviceToHost));
     if (type) RX_HIP(hipMemcpy(type, e.type, sizeof(int) * n, hipMemcpyDeviceToHost));
     if (q) RX_HIP(hipMemcpy(q, e.q, sizeof(double) * n, hipMemcpyDeviceToHost));
-    std::vector<double> tmp(n);
-    auto pull3 = [&](double *const src[3], double *dst) {
-      for (int a = 0; a < 3; ++a) {
-        RX_HIP(hipMemcpy(tmp.data(), src[a], sizeof(double) * n, hipMemcpyDeviceToHost));
-        for (int i = 0; i < n; ++i) dst[3 * static_cast<size_t>(i) + a] = tmp[i];
-      }
-    };
-    if (pos) pull3(e.pos, pos);
-    if (v) pull3(e.vel, v);
-    if (f) pull3(e.frc, f);
+    if (pos) pull3(e.pos, n, pos);
+    if (v) pull3(e.vel, n, v);
+    if (f) pull3(e.frc, n, f);
+    return n;
   });
-  return rc < 0 ? rc : n;
 }
 
 int rxmd_hip_set_charges(rxmd_handle h, int natoms, const double *q) {
@@ -129,17 +156,12 @@ int rxmd_hip_set_charges(rxmd_handle h, int natoms, const double *q) {
 int rxmd_hip_set_velocities(rxmd_handle h, int natoms, const double *v) {
   return guarded(h, [&](Engine &e) {
     if (natoms != e.N || !v) throw EngineError(RXMD_E_ARG, "natoms mismatch");
-    std::vector<double> tmp(natoms);
-    for (int a = 0; a < 3; ++a) {
-      for (int i = 0; i < natoms; ++i) tmp[i] = v[3 * static_cast<size_t>(i) + a];
-      RX_HIP(hipMemcpy(e.vel[a], tmp.data(), sizeof(double) * natoms, hipMemcpyHostToDevice));
-    }
+    push3(v, natoms, e.vel);
   });
 }
 
 int rxmd_hip_get_bonds(rxmd_handle h, int capacity, int maxnb, int *count, long long *partner_gid, double *bo) {
-  int n = 0;
-  const int rc = guarded(h, [&](Engine &e) {
+  return count_or_error(h, [&](Engine &e) {
     if (!count || !partner_gid || !bo || capacity < e.N || maxnb < e.MAXNB) throw EngineError(RXMD_E_ARG, "capacity smaller than natoms or maxnb smaller than MAXNEIGHBS");
     if (!e.lists_valid) throw EngineError(RXMD_E_STATE, "no bond lists: call rxmd_hip_force first");
     RX_HIP(hipStreamSynchronize(e.stream));
@@ -160,36 +182,25 @@ int rxmd_hip_get_bonds(rxmd_handle h, int capacity, int maxnb, int *count, long 
         bo[static_cast<size_t>(i) * maxnb + s] = b[static_cast<size_t>(off[i]) + s];
       }
     }
-    n = N;
+    return N;
   });
-  return rc ? rc : n;
 }
 
 int rxmd_hip_get_shells(rxmd_handle h, double *spos3, int capacity) {
-  int n = 0;
-  const int rc = guarded(h, [&](Engine &e) {
+  return count_or_error(h, [&](Engine &e) {
     if (!e.ff.pqeq) throw EngineError(RXMD_E_STATE, "the engine was created without a PQEq parameter file");
     if (!spos3 || capacity < e.N) throw EngineError(RXMD_E_ARG, "capacity smaller than natoms");
     RX_HIP(hipStreamSynchronize(e.stream));
-    std::vector<double> tmp(e.N);
-    for (int a = 0; a < 3; ++a) {
-      RX_HIP(hipMemcpy(tmp.data(), e.shl[a], sizeof(double) * e.N, hipMemcpyDeviceToHost));
-      for (int i = 0; i < e.N; ++i) spos3[3 * static_cast<size_t>(i) + a] = tmp[i];
-    }
-    n = e.N;
+    pull3(e.shl, e.N, spos3);
+    return e.N;
   });
-  return rc ? rc : n;
 }
 
 int rxmd_hip_set_shells(rxmd_handle h, int natoms, const double *spos3) {
   return guarded(h, [&](Engine &e) {
     if (!e.ff.pqeq) throw EngineError(RXMD_E_STATE, "the engine was created without a PQEq parameter file");
     if (natoms != e.N || !spos3) throw EngineError(RXMD_E_ARG, "natoms mismatch");
-    std::vector<double> tmp(natoms);
-    for (int a = 0; a < 3; ++a) {
-      for (int i = 0; i < natoms; ++i) tmp[i] = spos3[3 * static_cast<size_t>(i) + a];
-      RX_HIP(hipMemcpy(e.shl[a], tmp.data(), sizeof(double) * natoms, hipMemcpyHostToDevice));
-    }
+    push3(spos3, natoms, e.shl);
     e.lists_valid = false;
   });
 }
@@ -219,15 +230,11 @@ int rxmd_hip_step(rxmd_handle h, int nsteps) {
 }
 
 int rxmd_hip_minimise(rxmd_handle h, double ftol, int max_loops, double *pe, long long *evaluations) {
-  int loops = 0;
-  const int rc = guarded(h, [&](Engine &e) { e.eval_natoms = -1; loops = e.minimise(ftol, max_loops > 0 ? max_loops : 500, pe, evaluations); });
-  return rc ? rc : loops;
+  return count_or_error(h, [&](Engine &e) { e.eval_natoms = -1; return e.minimise(ftol, max_loops > 0 ? max_loops : 500, pe, evaluations); });
 }
 
 int rxmd_hip_last_qeq_iters(rxmd_handle h) {
-  int n = 0;
-  const int rc = guarded(h, [&](Engine &e) { n = e.nstep_qeq; });
-  return rc ? rc : n;
+  return count_or_error(h, [&](Engine &e) { return e.nstep_qeq; });
 }
 
 int rxmd_hip_thermostat(rxmd_handle h, int mdmode, double treq_K, double vsfact, double gke_per_atom) {
@@ -328,13 +335,15 @@ static void upload_reference_arrays(Engine &e, int nbuffer, int natoms, const do
     if (lex) { o[8] = e.lex_p[i]; o[9] = e.lex_v[i]; }
   }
   e.set_atoms_rxff(natoms, rec.data());
-  // keep the caller's real coordinates bit for bit (the record round trip is only used for sizing/setup)
-  std::vector<double> tmp(natoms);
-  for (int a = 0; a < 3; ++a) {
-    for (int i = 0; i < natoms; ++i) tmp[i] = pos[a * static_cast<size_t>(nbuffer) + i];
-    RX_HIP(hipMemcpy(e.pos[a], tmp.data(), sizeof(double) * natoms, hipMemcpyHostToDevice));
-  }
+  // keep the caller's real coordinates bit for bit (the record round trip is only used for sizing/setup); pos(NBUFFER,3): component a is contiguous
+  for (int a = 0; a < 3; ++a) RX_HIP(hipMemcpy(e.pos[a], pos + a * static_cast<size_t>(nbuffer), sizeof(double) * natoms, hipMemcpyHostToDevice));
 }
+// what a call in the reference's shapes hands back: f(NBUFFER,3) column-major -- component a of the residents is contiguous -- and the energies; the charges
+static void download_forces(Engine &e, int nbuffer, int natoms, double *f, double pe[14]) {
+  for (int a = 0; a < 3; ++a) RX_HIP(hipMemcpy(f + a * static_cast<size_t>(nbuffer), e.frc[a], sizeof(double) * natoms, hipMemcpyDeviceToHost));
+  if (pe) std::memcpy(pe, e.pe, sizeof(double) * 14);
+}
+static void download_charges(Engine &e, int natoms, double *q) { RX_HIP(hipMemcpy(q, e.q, sizeof(double) * natoms, hipMemcpyDeviceToHost)); }
 
 // isQEq = 2 starts the single CG step from qs = fqs*qsfp + (1-fqs)*q (qeq.F90:51-57): the host's qsfp must have come with put_lex
 static void require_lex(Engine &e, int natoms) {
@@ -362,7 +371,7 @@ int rxmd_hip_QEq(rxmd_handle h, int nbuffer, int natoms, const double *atype, co
     upload_reference_arrays(e, nbuffer, natoms, atype, pos, q);
     e.lex_pending = false;
     e.qeq();
-    RX_HIP(hipMemcpy(q, e.q, sizeof(double) * natoms, hipMemcpyDeviceToHost));
+    download_charges(e, natoms, q);
   });
 }
 
@@ -371,9 +380,7 @@ int rxmd_hip_FORCE(rxmd_handle h, int nbuffer, int natoms, const double *atype, 
   return guarded(h, [&](Engine &e) {
     upload_reference_arrays(e, nbuffer, natoms, atype, pos, q);
     e.force();
-    for (int a = 0; a < 3; ++a)                      // f(NBUFFER,3) column-major: component a of the residents is contiguous
-      RX_HIP(hipMemcpy(f + a * static_cast<size_t>(nbuffer), e.frc[a], sizeof(double) * natoms, hipMemcpyDeviceToHost));
-    if (pe) std::memcpy(pe, e.pe, sizeof(double) * 14);
+    download_forces(e, nbuffer, natoms, f, pe);
   });
 }
 
@@ -391,7 +398,7 @@ int rxmd_hip_PQEq(rxmd_handle h, int nbuffer, int natoms, const double *atype, c
     e.lex_pending = false;
     upload_shells(e, nbuffer, natoms, spos);
     e.qeq();
-    RX_HIP(hipMemcpy(q, e.q, sizeof(double) * natoms, hipMemcpyDeviceToHost));
+    download_charges(e, natoms, q);
     for (int a = 0; a < 3; ++a) RX_HIP(hipMemcpy(spos + a * static_cast<size_t>(nbuffer), e.shl[a], sizeof(double) * natoms, hipMemcpyDeviceToHost));
   });
 }
@@ -401,9 +408,7 @@ int rxmd_hip_FORCE_pqeq(rxmd_handle h, int nbuffer, int natoms, const double *at
     upload_reference_arrays(e, nbuffer, natoms, atype, pos, q);
     upload_shells(e, nbuffer, natoms, spos);
     e.force();
-    for (int a = 0; a < 3; ++a)                      // f(NBUFFER,3) column-major: component a of the residents is contiguous
-      RX_HIP(hipMemcpy(f + a * static_cast<size_t>(nbuffer), e.frc[a], sizeof(double) * natoms, hipMemcpyDeviceToHost));
-    if (pe) std::memcpy(pe, e.pe, sizeof(double) * 14);
+    download_forces(e, nbuffer, natoms, f, pe);
   });
 }
 
@@ -415,16 +420,12 @@ int rxmd_hip_evaluate_device(rxmd_handle h, int natoms, const long long *gid, co
 
 long long rxmd_hip_get_bonds_device(rxmd_handle h, int flags, double bo_min, long long capacity, long long *src, long long *dst, double *bo,
                                     double *bo3, double *vec3, void *stream) {
-  long long n = 0;
-  const int rc = guarded(h, [&](Engine &e) { n = e.bonds_device(flags, bo_min, capacity, src, dst, bo, bo3, vec3, static_cast<hipStream_t>(stream)); });
-  return rc < 0 ? rc : n;
+  return count_or_error(h, [&](Engine &e) { return e.bonds_device(flags, bo_min, capacity, src, dst, bo, bo3, vec3, static_cast<hipStream_t>(stream)); });
 }
 
 long long rxmd_hip_get_pairs_device(rxmd_handle h, int flags, double r_cut, long long capacity, long long *src, long long *dst, int *shift3, double *vec3,
                                     double *hval, void *stream) {
-  long long n = 0;
-  const int rc = guarded(h, [&](Engine &e) { n = e.pairs_device(flags, r_cut, capacity, src, dst, shift3, vec3, hval, static_cast<hipStream_t>(stream)); });
-  return rc < 0 ? rc : n;
+  return count_or_error(h, [&](Engine &e) { return e.pairs_device(flags, r_cut, capacity, src, dst, shift3, vec3, hval, static_cast<hipStream_t>(stream)); });
 }
 
 int rxmd_hip_bonds_vjp_device(rxmd_handle h, int flags, double bo_min, long long E, const double *grad_bo, const double *grad_bo3,
@@ -475,51 +476,44 @@ int rxmd_hip_set_qeq_mode(rxmd_handle h, int mode) {
 }
 
 int rxmd_hip_get_table(rxmd_handle h, int which, double *out, int capacity) {
-  int n = 0;
-  const int rc = guarded(h, [&](Engine &e) {
+  return count_or_error(h, [&](Engine &e) {
     if (!e.tables_ready) throw EngineError(RXMD_E_STATE, "tables are built when atoms are first set");
-    n = e.ff.nboty;
+    const int n = e.ff.nboty;
     if (!out || capacity < n * rxmd::NTABLE) throw EngineError(RXMD_E_ARG, "capacity too small");
-    const std::vector<double> *src[5] = {&e.ff.tblEvdw, &e.ff.tbldEvdw, &e.ff.tblEclmb, &e.ff.tbldEclmb, &e.ff.tblQEq};
     if (which < 0 || which > 4) throw EngineError(RXMD_E_ARG, "which must be 0..4");
-    for (int r = 1; r <= n; ++r)
-      for (int i = 1; i <= rxmd::NTABLE; ++i) out[static_cast<size_t>(r - 1) * rxmd::NTABLE + (i - 1)] = (*src[which])[static_cast<size_t>(r) * (rxmd::NTABLE + 2) + i];
+    dense_table(e.ff, which, out);
+    return n;
   });
-  return rc < 0 ? rc : n;
 }
 
 int rxmd_hip_get_cutoffs(rxmd_handle h, double *rc, int capacity, double *maxrc) {
-  int n = 0;
-  const int r = guarded(h, [&](Engine &e) {
+  return count_or_error(h, [&](Engine &e) {
     if (!e.tables_ready) throw EngineError(RXMD_E_STATE, "cutoffs are computed when atoms are first set");
-    n = e.ff.nboty;
+    const int n = e.ff.nboty;
     if (rc) { if (capacity < n) throw EngineError(RXMD_E_ARG, "capacity too small"); for (int k = 1; k <= n; ++k) rc[k - 1] = e.ff.bond[k].rc; }
     if (maxrc) *maxrc = e.ff.maxrc;
+    return n;
   });
-  return r < 0 ? r : n;
 }
 
 int rxmd_hip_debug_get(rxmd_handle h, int what, double *out, int capacity) {
-  int n = 0;
-  const int rc = guarded(h, [&](Engine &e) {
+  return count_or_error(h, [&](Engine &e) {
     if (!e.atoms_set) throw EngineError(RXMD_E_STATE, "atoms were never set");
     RX_HIP(hipStreamSynchronize(e.stream));
-    auto pull_d = [&](const double *src, int cnt, int stride, int off) {
-      std::vector<double> t(cnt);
-      RX_HIP(hipMemcpy(t.data(), src, sizeof(double) * cnt, hipMemcpyDeviceToHost));
-      for (int i = 0; i < cnt; ++i) out[static_cast<size_t>(i) * stride + off] = t[i];
-    };
+    auto need = [&](int k) { if (capacity < k) throw EngineError(RXMD_E_ARG, "capacity"); };
+    auto pull_d = [&](const double *src, int cnt) { RX_HIP(hipMemcpy(out, src, sizeof(double) * cnt, hipMemcpyDeviceToHost)); };
     const int G = e.G, N = e.N;
+    int n = 0;
     switch (what) {
-      case 0: n = G; if (capacity < n) throw EngineError(RXMD_E_ARG, "capacity"); pull_d(e.delta, G, 1, 0); break;
-      case 1: n = G; if (capacity < n) throw EngineError(RXMD_E_ARG, "capacity"); pull_d(e.deltap, G, 1, 0); break;
-      case 2: { n = G; if (capacity < n) throw EngineError(RXMD_E_ARG, "capacity"); std::vector<int> t(G); RX_HIP(hipMemcpy(t.data(), e.nbrcnt, sizeof(int) * G, hipMemcpyDeviceToHost)); for (int i = 0; i < G; ++i) out[i] = t[i]; break; }
-      case 3: n = G; if (capacity < 3 * n) throw EngineError(RXMD_E_ARG, "capacity"); for (int a = 0; a < 3; ++a) pull_d(e.pos[a], G, 3, a); break;
-      case 4: { n = G; if (capacity < n) throw EngineError(RXMD_E_ARG, "capacity"); std::vector<long long> t(G); RX_HIP(hipMemcpy(t.data(), e.gid, sizeof(long long) * G, hipMemcpyDeviceToHost)); for (int i = 0; i < G; ++i) out[i] = static_cast<double>(t[i]); break; }
-      case 5: { n = G; if (capacity < n) throw EngineError(RXMD_E_ARG, "capacity"); std::vector<int> t(G); RX_HIP(hipMemcpy(t.data(), e.type, sizeof(int) * G, hipMemcpyDeviceToHost)); for (int i = 0; i < G; ++i) out[i] = t[i]; break; }
-      case 6: { n = N; if (capacity < n) throw EngineError(RXMD_E_ARG, "capacity"); std::vector<int> t(N); RX_HIP(hipMemcpy(t.data(), e.n10, sizeof(int) * N, hipMemcpyDeviceToHost)); for (int i = 0; i < N; ++i) out[i] = t[i] & rxmd::N10_COUNT; break; }
+      case 0: n = G; need(n); pull_d(e.delta, G); break;
+      case 1: n = G; need(n); pull_d(e.deltap, G); break;
+      case 2: n = G; need(n); pull_as_double(e.nbrcnt, G, out); break;
+      case 3: n = G; need(3 * n); pull3(e.pos, G, out); break;
+      case 4: n = G; need(n); pull_as_double(e.gid, G, out); break;
+      case 5: n = G; need(n); pull_as_double(e.type, G, out); break;
+      case 6: n = N; need(n); pull_as_double(e.n10, N, out, rxmd::N10_COUNT); break;
       case 7: {
-        n = N; if (capacity < n) throw EngineError(RXMD_E_ARG, "capacity");
+        n = N; need(n);
         std::vector<int> c(N); RX_HIP(hipMemcpy(c.data(), e.n10, sizeof(int) * N, hipMemcpyDeviceToHost));
         for (int &v : c) v &= rxmd::N10_COUNT;
         std::vector<double> row(e.S10);
@@ -532,24 +526,24 @@ int rxmd_hip_debug_get(rxmd_handle h, int what, double *out, int capacity) {
         }
         break;
       }
-      case 8: n = G; if (capacity < n) throw EngineError(RXMD_E_ARG, "capacity"); pull_d(e.cd, G, 1, 0); break;
-      case 9: n = G; if (capacity < n) throw EngineError(RXMD_E_ARG, "capacity"); pull_d(e.q, G, 1, 0); break;
-      case 10: n = G; if (capacity < n) throw EngineError(RXMD_E_ARG, "capacity"); pull_d(e.cc_, G, 1, 0); break;
+      case 8: n = G; need(n); pull_d(e.cd, G); break;
+      case 9: n = G; need(n); pull_d(e.q, G); break;
+      case 10: n = G; need(n); pull_d(e.cc_, G); break;
       case 14: {   // RXMD_POISON_ALLOC: {1 if the pattern is on, the LAST entry of row 0 of the 10 A value array} -- an element no kernel writes (rows are shorter than their slot)
-        n = 2; if (capacity < 2) throw EngineError(RXMD_E_ARG, "capacity");
+        n = 2; need(2);
         out[0] = rxmd::poison_enabled() ? 1.0 : 0.0;
         RX_HIP(hipMemcpy(out + 1, e.hess + (e.S10 - 1), sizeof(double), hipMemcpyDeviceToHost));
         break;
       }
-      case 15: n = 2; if (capacity < 2) throw EngineError(RXMD_E_ARG, "capacity"); out[0] = e.nb10_valid ? 1.0 : 0.0; out[1] = e.nb10_sticky ? 1.0 : 0.0; break;   // the last list build wrote the 4-byte entries / a reader found them missing once (lists.hip: needs_nb10)
+      case 15: n = 2; need(2); out[0] = e.nb10_valid ? 1.0 : 0.0; out[1] = e.nb10_sticky ? 1.0 : 0.0; break;   // the last list build wrote the 4-byte entries / a reader found them missing once (lists.hip: needs_nb10)
       case 13: {   // Est of the start vector and after every CG iteration of the last QEq call (what the reference prints with -DQEQDUMP, qeq.F90:117)
-        n = static_cast<int>(e.est_trace.size()); if (capacity < n) throw EngineError(RXMD_E_ARG, "capacity");
+        n = static_cast<int>(e.est_trace.size()); need(n);
         for (int k = 0; k < n; ++k) out[k] = e.est_trace[k];
         break;
       }
       case 11: {   // window form of the 10 A matrix, checked on the host: per resident (atom order) the number of list entries whose 16-bit slot leads
                    // back to the entry's own cell-sorted position and ghost flag through the group's window (== n10 when the window is right; -1: no windows)
-        n = N; if (capacity < n) throw EngineError(RXMD_E_ARG, "capacity");
+        n = N; need(n);
         if (!e.win_valid) { for (int i = 0; i < N; ++i) out[i] = -1.0; break; }
         e.require_nb10();                                            // (a build that left the entries out is swept again; the engine keeps them from now on)
         RX_HIP(hipStreamSynchronize(e.stream));
@@ -580,20 +574,20 @@ int rxmd_hip_debug_get(rxmd_handle h, int what, double *out, int capacity) {
         break;
       }
       case 12: {   // read-bandwidth probe over the whole value array (a plain 16-byte-per-lane read; bench.py quotes the matrix pass next to it): out = {ms, bytes} for a few grid sizes
-        n = 4; if (capacity < 8) throw EngineError(RXMD_E_ARG, "capacity");
+        n = 4; need(8);
         const int grids[4] = {2048, 8192, 32768, 131072};
         for (int g = 0; g < 4; ++g) { out[2 * g] = rxmd::stream_probe_ms(e, grids[g]); out[2 * g + 1] = static_cast<double>(e.rows10) * e.S10 * 8.0; }
         n = 8; break;
       }
 #ifdef RXMD_EXPERIMENTS
-      case 104: n = 20; if (capacity < 20) throw EngineError(RXMD_E_ARG, "capacity"); rxmd::spmv_isolated_ms(e, out); break;   // real window pass / row pass back to back (experiments)
-      case 105: n = 5; if (capacity < 5) throw EngineError(RXMD_E_ARG, "capacity"); rxmd::spmv_tile_probe_ms(e, out); break;   // half-storage pass over 3-D tiles: timing probe (experiments)
-      case 102: n = 7; if (capacity < 7) throw EngineError(RXMD_E_ARG, "capacity"); rxmd::spmv_bisect_ms(e, out); break;   // stripped-down forms of the row kernel (experiments)
+      case 104: n = 20; need(20); rxmd::spmv_isolated_ms(e, out); break;   // real window pass / row pass back to back (experiments)
+      case 105: n = 5; need(5); rxmd::spmv_tile_probe_ms(e, out); break;   // half-storage pass over 3-D tiles: timing probe (experiments)
+      case 102: n = 7; need(7); rxmd::spmv_bisect_ms(e, out); break;   // stripped-down forms of the row kernel (experiments)
 #endif
       default: throw EngineError(RXMD_E_ARG, "unknown debug tap");
     }
+    return n;
   });
-  return rc < 0 ? rc : n;
 }
 
 int rxmd_hip_copy_to_host(const double *dev, double *host, long long n) {
@@ -715,9 +709,7 @@ int rxmd_host_ffield_table(const char *ffield_path, const long long *npt, int wh
   ff.build_tables();
   if (which >= 0 && which <= 4) {
     if (capacity < static_cast<long long>(ff.nboty) * rxmd::NTABLE) return RXMD_E_ARG;
-    const std::vector<double> *src[5] = {&ff.tblEvdw, &ff.tbldEvdw, &ff.tblEclmb, &ff.tbldEclmb, &ff.tblQEq};
-    for (int r = 1; r <= ff.nboty; ++r)
-      for (int i = 1; i <= rxmd::NTABLE; ++i) out[static_cast<size_t>(r - 1) * rxmd::NTABLE + (i - 1)] = (*src[which])[static_cast<size_t>(r) * (rxmd::NTABLE + 2) + i];
+    dense_table(ff, which, out);
   } else if (which == 5) {
     if (capacity < ff.nboty + 1) return RXMD_E_ARG;
     for (int r = 1; r <= ff.nboty; ++r) out[r - 1] = ff.bond[r].rc;

@@ -7,9 +7,7 @@
 // Single rank only: the atoms keep the caller's order because nothing migrates between ingest and egress.
 // rxmd_hip_get_bonds_device, at the end of the file, is the way OUT for the bond-order graph FORCE leaves in the compact bond tables: two more kernels
 //   k_bond_select / k_bond_fill   flag per table entry, exclusive sum, coordinate arrays (src, dst, bo, the three parts of bo, the bond vector)
-#include "engine.h"
-
-#include <hipcub/hipcub.hpp>
+#include "scan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -17,10 +15,6 @@
 #include <vector>
 
 namespace rxmd {
-
-static inline int nblk(long long n, int b) { return n > 0 ? static_cast<int>((n + b - 1) / b) : 1; }
-
-struct WrapBox { double H[9], Hi[9]; };   // row-major; column c of H is lattice vector a_(c+1) (GetBoxParams, init.F90:610-633)
 
 // What the ghost build and the cell binning expect of a resident is the state COPYATOMS(MODE_MOVE) leaves (exchange.hip, k_seg_count<true> with
 // dr = 0): an atom moves up when s <= 0 and down when lbox < s, s = Hi r - obox as xu2xs forms it, so residents have 0 < s <= lbox -- up to the
@@ -33,14 +27,14 @@ struct WrapBox { double H[9], Hi[9]; };   // row-major; column c of H is lattice
 //     r' = exactly one box length, s' = 1 to an ulp: inside the tolerance, left there.
 constexpr double WRAP_TOL = 1e-12;
 
-__device__ inline void to_normalised(const WrapBox &B, double r0, double r1, double r2, double (&s)[3]) {   // the expression of k_seg_count
+__device__ inline void to_normalised(const DevBox &B, double r0, double r1, double r2, double (&s)[3]) {   // the expression of k_seg_count
   s[0] = B.Hi[0] * r0 + B.Hi[1] * r1 + B.Hi[2] * r2;
   s[1] = B.Hi[3] * r0 + B.Hi[4] * r1 + B.Hi[5] * r2;
   s[2] = B.Hi[6] * r0 + B.Hi[7] * r1 + B.Hi[8] * r2;
 }
 
 // q_mode: 0 keep q (the previous call's solution, same natoms), 1 q = q_in, 2 q = 0
-__global__ void __launch_bounds__(256) k_ingest_device(int n, int nso, WrapBox B, const double *__restrict__ pos3, const int *__restrict__ type_in,
+__global__ void __launch_bounds__(256) k_ingest_device(int n, int nso, DevBox B, const double *__restrict__ pos3, const int *__restrict__ type_in,
                                                         const long long *__restrict__ gid_in, const double *__restrict__ q_in, int q_mode,
                                                         double *__restrict__ x, double *__restrict__ y, double *__restrict__ z,
                                                         double *__restrict__ vx, double *__restrict__ vy, double *__restrict__ vz,
@@ -116,20 +110,16 @@ void Engine::evaluate_device(int natoms, const long long *gid_d, const int *type
   if (cfg.isQEq == 2) throw EngineError(RXMD_E_ARG, "evaluate_device: isQEq = 2 is not available (the extended-Lagrangian state belongs to the integrator)");
   if (natoms < 1) throw EngineError(RXMD_E_ARG, "evaluate_device: natoms must be positive");
   if (!type_d || !pos3_d) throw EngineError(RXMD_E_ARG, "evaluate_device: type and pos3 must not be NULL");
-  if (!ev_io_in) { RX_HIP(hipEventCreateWithFlags(&ev_io_in, hipEventDisableTiming)); RX_HIP(hipEventCreateWithFlags(&ev_io_out, hipEventDisableTiming)); }
   const int warm_n = eval_natoms;
   if (!tables_ready) size_from_device_arrays(natoms, type_d, pos3_d, user);
   if (natoms > rows10 || natoms >= NB) throw EngineError(RXMD_E_NBUFFER, "evaluate_device: more atoms than the engine was sized for (" + std::to_string(std::min(rows10, NB - 1)) + ")");
   sync_stream();                                   // nothing of the previous call may still read what is overwritten
   eval_natoms = -1;                                // (until this call has gone through)
   last_atype.clear();                              // the array-shaped entry points must not take these atoms for theirs
-  RX_HIP(hipEventRecord(ev_io_in, user));
-  RX_HIP(hipStreamWaitEvent(stream, ev_io_in, 0));
-  WrapBox B;
-  for (int a = 0; a < 3; ++a) for (int c = 0; c < 3; ++c) { B.H[3 * a + c] = box.H[a][c]; B.Hi[3 * a + c] = box.Hi[a][c]; }
+  UserStream io(this, user);
   for (int a = 0; a < 3; ++a) RX_HIP(hipMemsetAsync(frc[a], 0, sizeof(double) * NB, stream));
   const int q_mode = q_in_d ? 1 : (warm_n == natoms ? 0 : 2);
-  k_ingest_device<<<nblk(natoms, 256), 256, 0, stream>>>(natoms, ff.nso, B, pos3_d, type_d, gid_d, q_in_d, q_mode, pos[0], pos[1], pos[2], vel[0], vel[1], vel[2],
+  k_ingest_device<<<nblk(natoms, 256), 256, 0, stream>>>(natoms, ff.nso, dev_box(box), pos3_d, type_d, gid_d, q_in_d, q_mode, pos[0], pos[1], pos[2], vel[0], vel[1], vel[2],
                                                           q, qsfp, qsfv, type, gid, d_err, scal + SCAL_ASTR, scal + SCAL_EVAL_HEAD);
   N = natoms; G = natoms;
   atoms_set = true; lists_valid = false; ghosts_valid = false;
@@ -138,8 +128,7 @@ void Engine::evaluate_device(int natoms, const long long *gid_d, const int *type
   qeq();                                           // (isQEq = 0: returns at once, the charges are the caller's)
   force(true);                                     // the list build in front of either reports a type outside the ffield (RXMD_E_ARG)
   k_egress_device<<<nblk(natoms, 256), 256, 0, stream>>>(natoms, frc[0], frc[1], frc[2], q, f3_d, q_out_d, scal + SCAL_ASTR, scal + SCAL_EVAL_HEAD, h_scal + H_SCAL_EVAL_VIRIAL);
-  RX_HIP(hipEventRecord(ev_io_out, stream));
-  RX_HIP(hipStreamWaitEvent(user, ev_io_out, 0));
+  io.end();                                        // (in front of the NaN trap: the caller's stream is joined even when it throws)
   finish_force();                                  // the host wait of the call: energies, NaN trap
   if (pe_out) for (int k = 0; k < 14; ++k) pe_out[k] = pe[k];
   if (virial_out) for (int c = 0; c < 6; ++c) virial_out[c] = h_scal[H_SCAL_EVAL_VIRIAL + c];
@@ -160,8 +149,6 @@ __global__ void __launch_bounds__(256) k_bond_select(int n, double bo_min, const
   flag[o] = (o < n && (bo_min <= 0.0 || bo0[o] >= bo_min)) ? 1 : 0;
 }
 
-// The owner of a ghost partner: groot[j] where the self exchange filled it (the 26-segment build and the local staged build, exchange.hip), or the owner's
-// local index the staged exchange carries with every atom (gowner = index * 1024 + rank, k_pack_ghosts) when one rank runs through the transport.
 __global__ void __launch_bounds__(256) k_bond_fill(int n, int nres, int as_gid, const int *__restrict__ flag, const int *__restrict__ off,
                                                     const int *__restrict__ bown, const int *__restrict__ nbr, const double *__restrict__ bo0,
                                                     const double *__restrict__ bo1, const double *__restrict__ bo2, const double *__restrict__ bo3,
@@ -176,7 +163,7 @@ __global__ void __launch_bounds__(256) k_bond_fill(int n, int nres, int as_gid, 
   if (as_gid) { src[e] = gid[i]; dst[e] = gid[j]; }
   else {
     src[e] = i;
-    dst[e] = j < nres ? j : (gowner ? static_cast<int>(gowner[j] >> 10) : groot[j]);
+    dst[e] = j < nres ? j : ghost_owner(j, gowner, groot);
   }
   bo[e] = bo0[o];
   if (parts3) { parts3[3 * e] = bo1[o]; parts3[3 * e + 1] = bo2[o]; parts3[3 * e + 2] = bo3[o]; }
@@ -188,22 +175,9 @@ long long Engine::select_bonds(double bo_min) {
   if (force_pending) finish_force();               // (FORCE itself joins the bonded chain's stream and the halo stream in front of its end)
   const int n = nbonds_res;
   if (n <= 0) return 0;
-  if (!bg_flag || bufs.cap[G_BGRAPH] < bcap) {       // first use, or the bond tables have grown since
-    sync_stream();                                   // (the fill kernel of an earlier call may still read the old blocks)
-    bufs.free_group(G_BGRAPH); bufs.alloc_group(*this, G_BGRAPH, bcap);
-  }
-  size_t need = 0;
-  RX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, bg_flag, bg_off, n + 1, stream));
-  if (need > cubtmp_bytes) {                         // (sized at set-up for NB + 1 items; a dense box has more bonds than atom slots)
-    sync_stream();
-    bufs.free_group(G_CUBTMP); cubtmp_bytes = need + 256; bufs.alloc_group(*this, G_CUBTMP, cubtmp_bytes);
-  }
+  if (!bg_flag || bufs.cap[G_BGRAPH] < bcap) regrow_group(G_BGRAPH, bcap);   // first use, or the bond tables have grown since (the fill kernel of an earlier call may still read the old blocks)
   k_bond_select<<<nblk(static_cast<long long>(n) + 1, 256), 256, 0, stream>>>(n, bo_min, bo0, bg_flag);
-  size_t tb = cubtmp_bytes;
-  RX_HIP(hipcub::DeviceScan::ExclusiveSum(cubtmp, tb, bg_flag, bg_off, n + 1, stream));
-  RX_HIP(hipMemcpyAsync(h_cnt + 2, bg_off + n, sizeof(int), hipMemcpyDeviceToHost, stream));
-  sync_stream();
-  return h_cnt[2];
+  return exclusive_sum_total(bg_flag, bg_off, n);
 }
 
 long long Engine::bonds_device(int flags, double bo_min, long long capacity, long long *src_d, long long *dst_d, double *bo_d, double *bo3_d, double *vec3_d, hipStream_t user) {
@@ -218,13 +192,10 @@ long long Engine::bonds_device(int flags, double bo_min, long long capacity, lon
   const int n = nbonds_res;
   const long long E = select_bonds(bo_min);          // the host wait of the call
   if (count_only || capacity < E || E == 0) return E;
-  if (!ev_io_in) { RX_HIP(hipEventCreateWithFlags(&ev_io_in, hipEventDisableTiming)); RX_HIP(hipEventCreateWithFlags(&ev_io_out, hipEventDisableTiming)); }
-  RX_HIP(hipEventRecord(ev_io_in, user));            // whatever the caller's stream still does with the output arrays comes first
-  RX_HIP(hipStreamWaitEvent(stream, ev_io_in, 0));
+  UserStream io(this, user);                         // whatever the caller's stream still does with the output arrays comes first
   k_bond_fill<<<nblk(n, 256), 256, 0, stream>>>(n, N, as_gid ? 1 : 0, bg_flag, bg_off, bown, nbr, bo0, bo1, bo2, bo3, gid, groot, multi() ? gowner : nullptr,
                                                 pos[0], pos[1], pos[2], src_d, dst_d, bo_d, bo3_d, vec3_d);
-  RX_HIP(hipEventRecord(ev_io_out, stream));
-  RX_HIP(hipStreamWaitEvent(user, ev_io_out, 0));
+  io.end();
   return E;
 }
 

@@ -141,6 +141,24 @@ __device__ inline int xcd_swizzle(int bid, int nwg) {
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
 }
 
+inline int nblk(long long n, int b) { return n > 0 ? static_cast<int>((n + b - 1) / b) : 1; }   // workgroups of b lanes for n items; an empty rank still launches (kernels guard their range)
+
+// The lattice for a kernel, by value: row-major, column c of H is lattice vector a_(c+1) (GetBoxParams, init.F90:610-633); Hi = H^-1
+struct DevBox { double H[9], Hi[9]; };
+inline DevBox dev_box(const Box &b) {
+  DevBox d;
+  for (int a = 0; a < 3; ++a) for (int c = 0; c < 3; ++c) { d.H[3 * a + c] = b.H[a][c]; d.Hi[3 * a + c] = b.Hi[a][c]; }
+  return d;
+}
+
+// The owner of ghost j among the residents of a single rank.  Two sources: groot[j] where the self exchange filled it (the 26-segment build and the
+// local staged build, exchange.hip), or, when one rank runs through the transport (Engine::multi(): the host then passes gowner, else nullptr), the
+// owner's local index that the staged exchange carries with every atom (gowner = index * 1024 + rank, k_pack_ghosts).  With several ranks the owner
+// is on another rank and nothing asks for it (global ids only: the host refuses the rest).
+__device__ inline int ghost_owner(int j, const long long *__restrict__ gowner, const int *__restrict__ groot) {
+  return gowner ? static_cast<int>(gowner[j] >> 10) : groot[j];
+}
+
 // Sum of a double over the 64 lanes of a wavefront, the total returned to every lane.  HIP's __shfl_xor compiles to ds_bpermute (two per
 // double and step: 12 dependent LDS-crossbar round trips per sum); this form stays in the vector ALU: four steps inside each row of 16
 // lanes with DPP lane permutations (quad swaps, half-row mirror, row mirror), two row broadcasts (lane 15 -> next row, lane 31 -> upper
@@ -325,7 +343,7 @@ struct Engine {
   double *partials = nullptr;  // [nblocks_red * 16]
   double *scal = nullptr;      // device scalars (CG state)
   double *h_scal = nullptr;    // pinned host mirror
-  int *d_err = nullptr, *h_err = nullptr, *h_cnt = nullptr;   // h_err: pinned, 4 ints of the device error word + 4 (h_cnt) for the counts the host waits for
+  int *d_err = nullptr, *h_err = nullptr, *h_cnt = nullptr;   // h_err: pinned, H_ERR_INTS ints: H_ERR_WORDS of the device error words, then h_cnt, the counts the host waits for (H_CNT_*)
   double *xbuf_send = nullptr, *xbuf_recv = nullptr; size_t xbuf_doubles = 0; bool xbuf_owned = false;   // staged-exchange message buffers
   double pe[14] = {0}, astr[6] = {0};
 
@@ -375,6 +393,31 @@ struct Engine {
                        double pe_out[14], double virial_out[6], hipStream_t user);
   void size_from_device_arrays(int natoms, const int *type_d, const double *pos3_d, hipStream_t user);
   hipEvent_t ev_io_in = nullptr, ev_io_out = nullptr;
+  // The scope of that join, for every call that works on the caller's device arrays: entered, `stream` waits for what `user` has queued so far; at end()
+  // -- or from the destructor on the way out of the block, an exception included -- `user` waits for what the block queued on `stream`, so that no way
+  // out leaves the caller's stream unordered behind the engine's work on the caller's arrays.  The two events are created on first use.
+  struct UserStream {
+    Engine &e; const hipStream_t user; bool open = false;
+    UserStream(Engine *eng, hipStream_t user_) : e(*eng), user(user_) {
+      if (!e.ev_io_in) { RX_HIP(hipEventCreateWithFlags(&e.ev_io_in, hipEventDisableTiming)); RX_HIP(hipEventCreateWithFlags(&e.ev_io_out, hipEventDisableTiming)); }
+      RX_HIP(hipEventRecord(e.ev_io_in, user));
+      RX_HIP(hipStreamWaitEvent(e.stream, e.ev_io_in, 0));
+      open = true;
+    }
+    void end() {
+      if (!open) return;
+      open = false;
+      RX_HIP(hipEventRecord(e.ev_io_out, e.stream));
+      RX_HIP(hipStreamWaitEvent(user, e.ev_io_out, 0));
+    }
+    ~UserStream() { try { end(); } catch (const EngineError &) {} }   // (on the way out an exception is already in flight, as in ~Timed)
+    UserStream(const UserStream &) = delete;
+  };
+  // a scratch group on first use or when it has to grow: nothing queued may still read the old blocks
+  void regrow_group(int group, size_t capacity = 0) { sync_stream(); bufs.free_group(group); bufs.alloc_group(*this, group, capacity); }
+  // scan.h (the export units only): exclusive sum of cnt[0 .. n] into off[0 .. n] on `stream` -- cnt[n] = 0, so off[n] is the total --, G_CUBTMP grown
+  // when n + 1 items need more than it holds, the total through the pinned slot H_CNT_EXPORT: ONE sync_stream(), the host wait of the caller
+  template <class T> long long exclusive_sum_total(T *cnt, T *off, int n);
   int eval_natoms = -1;
   // rxmd_hip_get_bonds_device (device_io.hip): the residents' part of the compact bond tables as coordinate (COO) arrays in DEVICE memory, entries with
   // bo0 >= bo_min in table order -- flag per entry, exclusive sum, fill.  src = dst = bo = nullptr: count only.  Returns the number selected; nothing is
@@ -626,6 +669,13 @@ constexpr unsigned NB10_GHOST = 1u << 30, NB10_SELF = 1u << 31;
 // n10[row] = entries of the row; bit 30: the row has a ghost partner (a boundary row of the domain).  The matrix pass needs the sums over
 // ghost columns only there (74 % of the rows of a 979,776-atom domain have none) and reads the flag with the length it needs anyway.
 constexpr int N10_GHOST_ROW = 1 << 30, N10_COUNT = N10_GHOST_ROW - 1;
+
+// the pinned block h_err in ints, and the slots of its second half h_cnt = h_err + H_ERR_WORDS: the selection totals of the one or two stages of an
+// exchange round (the first also takes the count of the atoms that stay, in front of the compaction of migrate(): never while a round is selected), and
+// the total of an export's exclusive sum (exclusive_sum_total: an int or a long long, 8 bytes at an 8-byte boundary)
+constexpr int H_ERR_WORDS = 16, H_ERR_INTS = 32;
+enum { H_CNT_ROUND0 = 0, H_CNT_ROUND1 = 1, H_CNT_EXPORT = 4 };
+static_assert(H_CNT_ROUND1 < H_CNT_EXPORT && H_CNT_EXPORT % 2 == 0 && H_ERR_WORDS % 2 == 0 && H_ERR_WORDS + H_CNT_EXPORT + 2 <= H_ERR_INTS, "the export total is 8 aligned bytes inside the pinned block, clear of the round counts");
 
 // device error codes written by kernels into Engine::d_err
 enum { DERR_NONE = 0, DERR_MAXNB = 1, DERR_MAXN10 = 2, DERR_GRID = 3, DERR_NBRINDX = 4, DERR_TYPE = 5 };

@@ -13,8 +13,6 @@ namespace rxmd {
 
 static const double UTIME = 1e3 / 20.455;  // reference src/module.F90:202
 static const int NMINCELL = 4;             // reference src/module.F90:84
-static inline int nblk(long long n, int b) { return n > 0 ? static_cast<int>((n + b - 1) / b) : 1; }   // an empty rank still launches (kernels guard their range)
-
 
 static void make_box(Box &b, const double lat[6], const int vprocs[3], const int vID[3]) {
   // GetBoxParams (reference src/init.F90:610-633)
@@ -367,7 +365,7 @@ void Engine::alloc_device() {
   partials_cap = std::max<size_t>(size_t(1) << 16, 4 * static_cast<size_t>(rows10) + 16384);   // up to one workgroup (4 partial sums) per row
   bufs.cap[G_CELLSTART] = cellstart_cap; bufs.cap[G_BOND] = bcap; bufs.cap[G_WIN] = win_ng_cap; bufs.cap[G_PARTIALS] = partials_cap;
   bufs.alloc_setup(*this);
-  h_cnt = h_err + 16;
+  h_cnt = h_err + H_ERR_WORDS;
   // hipcub scratch sized for the largest scan / sort we issue
   size_t b1 = 0, b2 = 0;
   hipcub::DeviceScan::ExclusiveSum(nullptr, b1, flags, scanout, NB + 1, stream);

@@ -19,8 +19,9 @@ static const int dinv_[7] = {0, 2, 1, 4, 3, 6, 5};     // comm.F90:60
 // kernels: coordinates, slab flags, append, halo
 struct BoxDev { double H[9], Hi[9], obox[3], lbox[3]; };
 static BoxDev boxdev(const Box &b) {
+  const DevBox m = dev_box(b);
   BoxDev d;
-  for (int a = 0; a < 3; ++a) for (int c = 0; c < 3; ++c) { d.H[3 * a + c] = b.H[a][c]; d.Hi[3 * a + c] = b.Hi[a][c]; }
+  for (int k = 0; k < 9; ++k) { d.H[k] = m.H[k]; d.Hi[k] = m.Hi[k]; }
   for (int a = 0; a < 3; ++a) { d.obox[a] = b.obox[a]; d.lbox[a] = b.lbox[a]; }
   return d;
 }
@@ -87,8 +88,6 @@ __global__ void k_fold_stage(int g0, int g1, const int *gsrc, double *fx, double
   fx[n] += fx[m]; fy[n] += fy[m]; fz[n] += fz[m];
 }
 
-static inline int nblk(long long n, int b) { return n > 0 ? static_cast<int>((n + b - 1) / b) : 1; }   // an empty rank still launches (kernels guard their range)
-
 // A walk over the six exchange stages goes round by round.  A round is one stage {d} or, where the + and the - stage of an axis travel together,
 // the two stages {d0, d0 + 1} of that axis: both scan the same atoms (residents and the ghosts of EARLIER axes, comm.F90:55-66), and their send
 // lists, ghost slots and messages lie back to back.  Forward {1,2},{3,4},{5,6} or {1}..{6}; the force fold walks the same rounds backwards.
@@ -109,9 +108,9 @@ void Engine::select_round(Round r, int nscan, double dr, int skip_dead, int tota
     size_t tb = cubtmp_bytes;
     RX_HIP(hipcub::DeviceScan::ExclusiveSum(cubtmp, tb, sel_flags(k), sel_scan(k), nscan + 1, stream));
   }
-  for (int k = 0; k < r.n; ++k) RX_HIP(hipMemcpyAsync(h_cnt + k, sel_scan(k) + nscan, sizeof(int), hipMemcpyDeviceToHost, stream));
+  for (int k = 0; k < r.n; ++k) RX_HIP(hipMemcpyAsync(h_cnt + H_CNT_ROUND0 + k, sel_scan(k) + nscan, sizeof(int), hipMemcpyDeviceToHost, stream));
   sync_stream();
-  total[0] = h_cnt[0]; total[1] = r.n > 1 ? h_cnt[1] : 0;   // counts arrive in pinned host memory
+  total[0] = h_cnt[H_CNT_ROUND0]; total[1] = r.n > 1 ? h_cnt[H_CNT_ROUND1] : 0;   // counts arrive in pinned host memory
 }
 
 void Engine::ghost_build() {
@@ -781,9 +780,9 @@ void Engine::migrate() {
     k_alive_flags<<<nblk(n + 1, 256), 256, 0, stream>>>(n, type, flags);
     size_t tb = cubtmp_bytes;
     RX_HIP(hipcub::DeviceScan::ExclusiveSum(cubtmp, tb, flags, scanout, n + 1, stream));
-    RX_HIP(hipMemcpyAsync(h_cnt + 0, scanout + n, sizeof(int), hipMemcpyDeviceToHost, stream));
+    RX_HIP(hipMemcpyAsync(h_cnt + H_CNT_ROUND0, scanout + n, sizeof(int), hipMemcpyDeviceToHost, stream));
     sync_stream();
-    newN = h_cnt[0];   // counts arrive in pinned host memory
+    newN = h_cnt[H_CNT_ROUND0];   // counts arrive in pinned host memory
     if (newN > rows10) throw EngineError(RXMD_E_NBUFFER, "resident count grew beyond the 10 A list capacity");
     // scratch: reuse force + bonded scratch arrays as compaction targets (they are recomputed every step)
     double *tmpd[9] = {frc[0], frc[1], frc[2], cds, cd, cc_, deltap, delta, nlp};

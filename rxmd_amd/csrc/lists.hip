@@ -13,8 +13,6 @@
 
 namespace rxmd {
 
-static inline int nblk(long long n, int b) { return n > 0 ? static_cast<int>((n + b - 1) / b) : 1; }   // an empty rank still launches (kernels guard their range)
-
 
 // ---- geometry of a sweep over the engine's grid ---------------------------------------------------------------------------
 // The atoms are sorted by (cell x, cell y, z-slice): column (x, y) is one contiguous run, ordered in z to the width of a slice

@@ -23,8 +23,6 @@
 
 namespace rxmd {
 
-static inline int nblk(long long n, int b) { return n > 0 ? static_cast<int>((n + b - 1) / b) : 1; }
-
 __global__ void k_axpy3(int n, double s, const double *__restrict__ px, const double *__restrict__ py, const double *__restrict__ pz,
                         double *__restrict__ x, double *__restrict__ y, double *__restrict__ z) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -15,16 +15,12 @@
 // the 2-byte window slot: sl10 & 0x7fff -> win_k of the row's group (rpos[i] / WIN_ROWS) -> first position of the slot's unit + offset in the unit.
 // Algorithmic bytes per LIST entry, count: 4 (entry) or 2 (slot) streamed + 4 (perm) + 24 (position) gathered; fill: the same again, + 8 for hval,
 // and per SELECTED entry 16 out (src, dst) + 24 (vec3) + 12 (shift3) + 8 (hval), + 4 or 8 gathered for a ghost's owner or a global id.
-#include "engine.h"
-
-#include <hipcub/hipcub.hpp>
+#include "scan.h"
 
 #include <cmath>
 #include <string>
 
 namespace rxmd {
-
-static inline int nblk(long long n, int b) { return n > 0 ? static_cast<int>((n + b - 1) / b) : 1; }
 
 constexpr int PG_ROWS = 4;                       // rows (wavefronts) of a workgroup
 
@@ -35,7 +31,6 @@ struct PairList {                                // what both kernels need to wa
   const unsigned short *sl10;
   const double *x, *y, *z;
 };
-struct PairBox { double H[9], Hi[9]; };          // row-major; column c of H is lattice vector a_(c+1)
 
 // cell-sorted position of entry kk of the row whose streams start at `row` (wk: the window of the row's group, slot route only); clamped into
 // [0, G) as the slot route of k_ehb_sweep is, so that a damaged stream cannot send the gathers behind it out of the arrays
@@ -76,10 +71,7 @@ __global__ void __launch_bounds__(64 * PG_ROWS) k_pair_count(PairList L, long lo
   if (lane == 0) cnt[i] = c;
 }
 
-// The owner of a ghost partner as k_bond_fill (device_io.hip) resolves it: groot[j] behind the self exchange, the owner's local index the staged
-// exchange carries (gowner = index * 1024 + rank) when one rank runs through the transport.  With several ranks (global ids only, no shift3: the
-// host refuses the rest) nothing asks for the owner.
-__global__ void __launch_bounds__(64 * PG_ROWS) k_pair_fill(PairList L, PairBox B, int as_gid, const long long *__restrict__ off, const double *__restrict__ hess,
+__global__ void __launch_bounds__(64 * PG_ROWS) k_pair_fill(PairList L, DevBox B, int as_gid, const long long *__restrict__ off, const double *__restrict__ hess,
                                                             const long long *__restrict__ gid, const int *__restrict__ groot, const long long *__restrict__ gowner,
                                                             long long *__restrict__ src, long long *__restrict__ dst, int *__restrict__ shift3,
                                                             double *__restrict__ vec3, double *__restrict__ hval) {
@@ -108,7 +100,7 @@ __global__ void __launch_bounds__(64 * PG_ROWS) k_pair_fill(PairList L, PairBox 
       const size_t e = static_cast<size_t>(base) + __popcll(m & ((1ULL << lane) - 1ULL));
       const bool ghost = j >= L.N;
       int own = j;
-      if (ghost && (!as_gid || shift3)) own = min(max(gowner ? static_cast<int>(gowner[j] >> 10) : groot[j], 0), L.N - 1);   // (clamped: its position is read below)
+      if (ghost && (!as_gid || shift3)) own = min(max(ghost_owner(j, gowner, groot), 0), L.N - 1);   // (clamped: its position is read below)
       src[e] = si;
       dst[e] = as_gid ? gid[j] : static_cast<long long>(own);
       if (vec3) { vec3[3 * e] = d0; vec3[3 * e + 1] = d1; vec3[3 * e + 2] = d2; }   // the ghost IS the right periodic image: no minimum-image step
@@ -133,25 +125,9 @@ long long Engine::select_pairs(double r_cut) {
   if (force_pending) finish_force();               // (FORCE itself joins the bonded chain's stream and the halo stream in front of its end)
   if (N <= 0) return 0;
   if (!nb10_valid && !win_valid) require_nb10();   // neither route to the partners exists (build_ghosts_and_lists sweeps such a build again: not met in practice)
-  if (!pg_cnt || pg_rows < rows10) {               // first use, or the rows have grown since
-    sync_stream();
-    bufs.free_group(G_PGRAPH); bufs.alloc_group(*this, G_PGRAPH);
-    pg_rows = rows10;
-  }
-  size_t need = 0;
-  RX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, pg_cnt, pg_off, N + 1, stream));
-  if (need > cubtmp_bytes) {
-    sync_stream();
-    bufs.free_group(G_CUBTMP); cubtmp_bytes = need + 256; bufs.alloc_group(*this, G_CUBTMP, cubtmp_bytes);
-  }
-  const PairList L = pair_list(r_cut);
-  k_pair_count<<<nblk(static_cast<long long>(N) + 1, PG_ROWS), 64 * PG_ROWS, 0, stream>>>(L, pg_cnt);
-  size_t tb = cubtmp_bytes;
-  RX_HIP(hipcub::DeviceScan::ExclusiveSum(cubtmp, tb, pg_cnt, pg_off, N + 1, stream));
-  long long *const h_total = reinterpret_cast<long long *>(h_cnt + 4);      // (h_cnt[0..2]: the exchange's and the bond graph's counts)
-  RX_HIP(hipMemcpyAsync(h_total, pg_off + N, sizeof(long long), hipMemcpyDeviceToHost, stream));
-  sync_stream();
-  return *h_total;
+  if (!pg_cnt || pg_rows < rows10) { regrow_group(G_PGRAPH); pg_rows = rows10; }   // first use, or the rows have grown since
+  k_pair_count<<<nblk(static_cast<long long>(N) + 1, PG_ROWS), 64 * PG_ROWS, 0, stream>>>(pair_list(r_cut), pg_cnt);
+  return exclusive_sum_total(pg_cnt, pg_off, N);
 }
 
 PairList Engine::pair_list(double r_cut) const {
@@ -176,15 +152,10 @@ long long Engine::pairs_device(int flags, double r_cut, long long capacity, long
   if (!atoms_set || !lists_valid) throw EngineError(RXMD_E_STATE, "no 10 A list: call rxmd_hip_qeq or rxmd_hip_force first");
   const long long E = select_pairs(r_cut);           // the host wait of the call
   if (count_only || capacity < E || E == 0) return E;
-  if (!ev_io_in) { RX_HIP(hipEventCreateWithFlags(&ev_io_in, hipEventDisableTiming)); RX_HIP(hipEventCreateWithFlags(&ev_io_out, hipEventDisableTiming)); }
-  RX_HIP(hipEventRecord(ev_io_in, user));            // whatever the caller's stream still does with the output arrays comes first
-  RX_HIP(hipStreamWaitEvent(stream, ev_io_in, 0));
-  PairBox B;
-  for (int a = 0; a < 3; ++a) for (int c = 0; c < 3; ++c) { B.H[3 * a + c] = box.H[a][c]; B.Hi[3 * a + c] = box.Hi[a][c]; }
-  k_pair_fill<<<nblk(N, PG_ROWS), 64 * PG_ROWS, 0, stream>>>(pair_list(r_cut), B, as_gid ? 1 : 0, pg_off, hess, gid, groot, multi() ? gowner : nullptr,
+  UserStream io(this, user);                         // whatever the caller's stream still does with the output arrays comes first
+  k_pair_fill<<<nblk(N, PG_ROWS), 64 * PG_ROWS, 0, stream>>>(pair_list(r_cut), dev_box(box), as_gid ? 1 : 0, pg_off, hess, gid, groot, multi() ? gowner : nullptr,
                                                              src_d, dst_d, shift3_d, vec3_d, hval_d);
-  RX_HIP(hipEventRecord(ev_io_out, stream));
-  RX_HIP(hipStreamWaitEvent(user, ev_io_out, 0));
+  io.end();
   return E;
 }
 

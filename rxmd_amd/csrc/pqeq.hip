@@ -13,7 +13,6 @@
 
 namespace rxmd {
 
-static inline int nblk(long long n, int b) { return n > 0 ? static_cast<int>((n + b - 1) / b) : 1; }   // an empty rank still launches (kernels guard their range)
 static constexpr double CEchrge = 23.02;     // module.F90:683
 static constexpr double Cclmb0 = 332.0638;   // module.F90:681
 

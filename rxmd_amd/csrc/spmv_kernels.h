@@ -9,8 +9,6 @@
 
 namespace rxmd {
 
-static inline int nblk(long long n, int b) { return n > 0 ? static_cast<int>((n + b - 1) / b) : 1; }   // an empty rank still launches (kernels guard their range)
-
 enum { MODE_HSH = 0, MODE_GRAD = 1 };      // (the CG scalars S_* and their snapshot slots: the layout block of engine.h)
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 #ifndef SPMV_UNR

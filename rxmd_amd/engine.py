@@ -27,6 +27,10 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _addr(a):      # a device address or a stream handle given as an integer (0: NULL) -> a void * argument
+    return C.c_void_p(int(a) or None)
+
+
 class RxmdEngine:
     """One engine = one rank of the vprocs grid = one MI355X."""
 
@@ -248,8 +252,7 @@ class RxmdEngine:
         float64 pos[natoms][3] anywhere in space, outputs float64 f[natoms][3] and q_out[natoms] (0: not wanted), optional int64 gid[natoms] and
         start charges q_in[natoms]; stream: the hipStream_t handle the arrays are produced and consumed on -> (PE(0:13), virial[6]) on the host"""
         pe = np.zeros(14); vir = np.zeros(6)
-        p = [C.c_void_p(int(a) or None) for a in (gid_ptr, type_ptr, pos_ptr, q_in_ptr, f_ptr, q_out_ptr)]
-        self._chk(self.L.rxmd_hip_evaluate_device(self.h, int(natoms), p[0], p[1], p[2], p[3], p[4], p[5], _ptr(pe), _ptr(vir), C.c_void_p(int(stream) or None)))
+        self._chk(self.L.rxmd_hip_evaluate_device(self.h, int(natoms), *map(_addr, (gid_ptr, type_ptr, pos_ptr, q_in_ptr, f_ptr, q_out_ptr)), _ptr(pe), _ptr(vir), _addr(stream)))
         return pe, vir
 
     def bonds_device(self, capacity, src_ptr, dst_ptr, bo_ptr, bo3_ptr=0, vec_ptr=0, bo_min=0.0, as_gid=False, stream=0):
@@ -258,17 +261,14 @@ class RxmdEngine:
         double-pi) and vec[capacity][3] (r_dst - r_src, the right periodic image).  Every list entry with bo >= bo_min, in the row-major order of
         bonds(); directed.  src / dst are local indices (the order of atoms()), global ids with as_gid.  src_ptr = dst_ptr = bo_ptr = 0: count only.
         -> E, the number of directed bonds selected; nothing is written when capacity < E"""
-        p = [C.c_void_p(int(a) or None) for a in (src_ptr, dst_ptr, bo_ptr, bo3_ptr, vec_ptr)]
-        return self._chk(self.L.rxmd_hip_get_bonds_device(self.h, BONDS_GID if as_gid else 0, float(bo_min), int(capacity), p[0], p[1], p[2], p[3], p[4],
-                                                          C.c_void_p(int(stream) or None)))
+        return self._chk(self.L.rxmd_hip_get_bonds_device(self.h, BONDS_GID if as_gid else 0, float(bo_min), int(capacity), *map(_addr, (src_ptr, dst_ptr, bo_ptr, bo3_ptr, vec_ptr)), _addr(stream)))
 
     def bonds_vjp_device(self, E, grad_pos_ptr, grad_bo_ptr=0, grad_bo3_ptr=0, grad_vec_ptr=0, bo_min=0.0, as_gid=False, stream=0):
         """the vector-Jacobian product of that graph with respect to the positions (include/rxmd_hip.h: rxmd_hip_bonds_vjp_device), device arrays given
         as integer addresses: float64 grad_bo[E], grad_bo3[E][3], grad_vec[E][3] (0: not given; at least one is) are dL/d(bo, bo3, vec) in the edge
         order of bonds_device(bo_min=bo_min, as_gid=as_gid) on the same FORCE state, E the count that call returns (RxmdError -1 otherwise, nothing
         written); float64 grad_pos[natoms][3] receives dL/dpos in the order of atoms() (overwritten)"""
-        p = [C.c_void_p(int(a) or None) for a in (grad_bo_ptr, grad_bo3_ptr, grad_vec_ptr, grad_pos_ptr)]
-        self._chk(self.L.rxmd_hip_bonds_vjp_device(self.h, BONDS_GID if as_gid else 0, float(bo_min), int(E), p[0], p[1], p[2], p[3], C.c_void_p(int(stream) or None)))
+        self._chk(self.L.rxmd_hip_bonds_vjp_device(self.h, BONDS_GID if as_gid else 0, float(bo_min), int(E), *map(_addr, (grad_bo_ptr, grad_bo3_ptr, grad_vec_ptr, grad_pos_ptr)), _addr(stream)))
 
     def pairs_device(self, capacity, src_ptr, dst_ptr, shift_ptr=0, vec_ptr=0, h_ptr=0, r_cut=0.0, as_gid=False, stream=0):
         """the 10 A pair graph of the last list build as coordinate arrays in device memory, given as integer addresses (include/rxmd_hip.h:
@@ -277,9 +277,7 @@ class RxmdEngine:
         |vec| <= r_cut (r_cut <= 0: the whole list; above the taper cut-off: RxmdError -1), in the order of atoms() and list order within an atom;
         directed, one edge per image.  src / dst are local indices, global ids with as_gid.  src_ptr = dst_ptr = 0: count only.
         -> E, the number of directed pairs selected; nothing is written when capacity < E"""
-        p = [C.c_void_p(int(a) or None) for a in (src_ptr, dst_ptr, shift_ptr, vec_ptr, h_ptr)]
-        return self._chk(self.L.rxmd_hip_get_pairs_device(self.h, PAIRS_GID if as_gid else 0, float(r_cut), int(capacity), p[0], p[1], p[2], p[3], p[4],
-                                                          C.c_void_p(int(stream) or None)))
+        return self._chk(self.L.rxmd_hip_get_pairs_device(self.h, PAIRS_GID if as_gid else 0, float(r_cut), int(capacity), *map(_addr, (src_ptr, dst_ptr, shift_ptr, vec_ptr, h_ptr)), _addr(stream)))
 
     # ---- introspection ----
     def stats(self):

@@ -31,11 +31,20 @@ from torch.autograd.function import once_differentiable
 from .engine import RxmdEngine
 
 
+def _check_real(name, v):
+    """ValueError unless v is a real number (a bool is not) -> float(v); touches no GPU"""
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError("%s must be a real number, got %s" % (name, type(v).__name__))
+    return float(v)
+
+
+def _check_bool(name, v):
+    if not isinstance(v, (bool, np.bool_)):
+        raise ValueError("%s must be a bool, got %s" % (name, type(v).__name__))
+
+
 def _check_bo_min(bo_min):
-    """ValueError unless bo_min is a real number (a bool is not); touches no GPU"""
-    if isinstance(bo_min, (bool, np.bool_)) or not isinstance(bo_min, (int, float, np.integer, np.floating)):
-        raise ValueError("bo_min must be a real number, got %s" % type(bo_min).__name__)
-    return float(bo_min)
+    return _check_real("bo_min", bo_min)
 
 
 def _check_pos(pos, natoms, device):
@@ -161,8 +170,7 @@ class ReaxFF:
             shift = torch.round((g["edge_vec"] - (pos[dst] - pos[src])) @ torch.linalg.inv(H).T)       # [E, 3] integers, constants
             d = (pos[dst] - pos[src] + shift @ H.T).norm(dim=1)                                       # differentiable in pos"""
         bo_min = _check_bo_min(bo_min)
-        if not isinstance(components, (bool, np.bool_)):
-            raise ValueError("components must be a bool, got %s" % type(components).__name__)
+        _check_bool("components", components)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             E = self.engine.bonds_device(0, 0, 0, 0, bo_min=bo_min, stream=stream)
@@ -203,11 +211,8 @@ class ReaxFF:
         an exact integer recovery -- and vec is RETURNED AS pos[dst] - pos[src] + n' @ cell, computed in torch: differentiable in pos, and in `cell`
         when that is given as a [3, 3] tensor (default: the engine's lattice, a constant), by plain autograd.  edge_index, shifts and h are constants:
         which pairs are selected is not differentiated, and h carries no gradient (no dH/dr)."""
-        if isinstance(r_cut, (bool, np.bool_)) or not isinstance(r_cut, (int, float, np.integer, np.floating)):
-            raise ValueError("r_cut must be a real number, got %s" % type(r_cut).__name__)
-        r_cut = float(r_cut)
-        if not isinstance(values, (bool, np.bool_)):
-            raise ValueError("values must be a bool, got %s" % type(values).__name__)
+        r_cut = _check_real("r_cut", r_cut)
+        _check_bool("values", values)
         if pos is not None:
             _check_pos(pos, self.natoms, self.device)
         if cell is not None and (not isinstance(cell, torch.Tensor) or cell.dtype != torch.float64 or cell.shape != (3, 3) or cell.device != self.device):
@@ -247,8 +252,7 @@ class ReaxFF:
         that finds another raises RuntimeError -- nothing is evaluated again behind the caller's back."""
         _check_pos(pos, self.natoms, self.device)
         bo_min = _check_bo_min(bo_min)
-        if not isinstance(components, (bool, np.bool_)):
-            raise ValueError("components must be a bool, got %s" % type(components).__name__)
+        _check_bool("components", components)
         energy, bo, vec, parts, edge, forces, charges = _BondOrders.apply(pos, self, bo_min, bool(components), q0)
         out = dict(energy=energy, edge_index=edge, bond_order=bo, edge_vec=vec, forces=forces, charges=charges)
         if components:
