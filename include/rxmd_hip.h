@@ -279,6 +279,44 @@ int rxmd_hip_bonds_vjp_device(rxmd_handle h, int flags, double bo_min, long long
 long long rxmd_hip_get_pairs_device(rxmd_handle h, int flags, double r_cut, long long capacity, long long *src, long long *dst, int *shift3,
                                     double *vec3, double *hval, void *stream);
 
+/* Structure statistics of a live engine, accumulated on the DEVICE from the 10 A list: partial pair counts (-> g_ab(r), n_ab(r), S_ab(q)) and
+ * bond-angle counts -- what the reference's offline util/stat computes from XYZ frames with a CPU voxel list.  The usual loop is
+ *   structure_begin; for (...) { rxmd_hip_step(h, every); rxmd_hip_structure_sample(h); }  structure_get; structure_end
+ * and rxmd_amd/structure.py holds the reference's normalisation of the counts.
+ * begin   allocates zeroed int64 accumulators on the device; calling it again replaces them (counts, volume sum and frames start from zero).
+ *         RXMD_E_ARG unless 0 < r_max <= the reach of the list (the taper cut-off: 10 A, 12.5 A on an engine created with pqeq_path; the rule of
+ *         rxmd_hip_get_pairs_device), 1 <= nbins_r <= 4096, 0 <= nshells <= 4, and for nshells > 0: angle_cut[nshells] strictly ascending with
+ *         0 < angle_cut[l] <= r_max, 1 <= nbins_angle <= 360 (nshells = 0: angle_cut and nbins_angle are ignored).  The reference's settings fit:
+ *         0.01 A bins (r_max 10, nbins_r 1000), three shells at 2, 4, 6 A, 180 angle bins.
+ * sample  adds the engine's current state; works on the engine's stream, no host wait beyond the end of a pending FORCE.  RXMD_E_STATE: no begin,
+ *         or no valid 10 A list (no rxmd_hip_qeq / rxmd_hip_force / evaluate / step yet, or set_atoms / set_lattice / set_charges /
+ *         set_qeq_precision since: the rule of rxmd_hip_get_pairs_device).  After rxmd_hip_step the state is that of the last step's FORCE.
+ *   pair_counts[(a nso + b) nbins_r + k] += 1 for every entry of a resident's row with r < r_max: a = the resident's type - 1, b = the partner's
+ *         type - 1, nso = the ffield's number of types, k = (int)(r nbins_r / r_max), r = |r_partner - r_resident| with the partner as the list
+ *         holds it (ghosts and images included).  DIRECTED and one per image, exactly the edges of rxmd_hip_get_pairs_device.
+ *   angle_counts[l][tj][ti][tk][m] += 1 and angle_counts[l][tk][ti][tj][m] += 1 (row-major, extents nshells, nso, nso, nso, nbins_angle) for every
+ *         resident i and every unordered pair of distinct entries j, k of its row with both r < angle_cut[l]: theta = acos(clamp(u_j . u_k, -1, 1))
+ *         180 / pi, m = min((int)(theta nbins_angle / 180), nbins_angle - 1).  This is TWICE the reference's table ba (util/stat/main.f90 books 0.5
+ *         each way): the counters stay integers.  The min is a designed deviation: the reference's int(theta) + 1 leaves its table at exactly 180.
+ *   atoms_per_type[a] += the residents of type a + 1; volume_sum += the TRUE volume of the whole box (the reference multiplies the three lengths:
+ *         right for orthorhombic cells only); frames += 1.
+ *         Integer atomics only: two samples of one state add identical counts, whatever the layout of the list.  Counts are PER RANK (the
+ *         convention of rxmd_hip_get_energy): a rank books its residents' rows, ghost partners as partners; the sum over the ranks is the whole
+ *         box, no collective is added (volume_sum and frames are the same on every rank: do not sum those).  Engines created with pqeq_path and
+ *         any vprocs work.  Completeness is that of the pair graph: the list is the full radius graph up to the shortest perpendicular width of the
+ *         box; a pair that needs an image two boxes away is not in it.
+ * get     copies the accumulators to the host; any pointer may be NULL; pair_counts holds nso nso nbins_r words, angle_counts nshells nso^3
+ *         nbins_angle, atoms_per_type nso; a capacity (in words) below the array size is RXMD_E_ARG and NOTHING is written.  It does not reset.
+ *         RXMD_E_STATE without a begin.
+ * end     frees the accumulators (no begin: nothing to do).
+ * set_atoms, set_lattice and set_qeq_precision between samples are fine: the accumulators persist, the next sample needs a fresh list as usual.
+ * An engine that never calls begin allocates and launches nothing for this.  No counterpart in the reference's engine. */
+int rxmd_hip_structure_begin(rxmd_handle h, double r_max, int nbins_r, int nshells, const double *angle_cut, int nbins_angle);
+int rxmd_hip_structure_sample(rxmd_handle h);
+int rxmd_hip_structure_get(rxmd_handle h, long long *pair_counts, long long pair_capacity, long long *angle_counts, long long angle_capacity,
+                           long long *atoms_per_type, double *volume_sum, long long *frames);
+int rxmd_hip_structure_end(rxmd_handle h);
+
 /* ---- introspection for tests, roofline accounting and the timers table (main.F90:135-182) ---- */
 typedef struct rxmd_stats {
   int natoms, nghost_qeq, nghost_force; /* copyptr(6)-NATOMS after the QEq / FORCE ghost builds */

@@ -84,6 +84,10 @@ SYMBOLS = [
     ("rxmd_hip_get_bonds_device", C.c_longlong, [H, C.c_int, C.c_double, C.c_longlong, PD, PD, PD, PD, PD, C.c_void_p]),
     ("rxmd_hip_get_pairs_device", C.c_longlong, [H, C.c_int, C.c_double, C.c_longlong, PD, PD, PD, PD, PD, C.c_void_p]),
     ("rxmd_hip_bonds_vjp_device", C.c_int,[H, C.c_int, C.c_double, C.c_longlong, PD, PD, PD, PD, C.c_void_p]),
+    ("rxmd_hip_structure_begin", C.c_int, [H, C.c_double, C.c_int, C.c_int, PD, C.c_int]),
+    ("rxmd_hip_structure_sample", C.c_int, [H]),
+    ("rxmd_hip_structure_get", C.c_int, [H, PD, C.c_longlong, PD, C.c_longlong, PD, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
+    ("rxmd_hip_structure_end", C.c_int, [H]),
     ("rxmd_hip_get_stats", C.c_int, [H, C.POINTER(RxmdStats)]),
     ("rxmd_hip_reset_timers", C.c_int, [H]),
     ("rxmd_hip_PQEq", C.c_int, [H, C.c_int, C.c_int, PD, PD, PD, PD]),

@@ -198,6 +198,10 @@ void Engine::declare_buffers() {
   // first use allocates them at the rows10 of that day (Engine::select_pairs re-allocates when the rows have grown); an engine that never asks has neither
   b.add(pg_cnt, G_PGRAPH, Dim::Rows10, 1, 1, P, never);
   b.add(pg_off, G_PGRAPH, Dim::Rows10, 1, 1, P, never);
+  // rxmd_hip_structure_* (structure.hip): the int64 accumulators of the structure statistics, capacity = the words structure_begin asked for; zeros
+  // are the protocol; resident: they outlive a capacity change (Engine::grow_capacity allocates the group again in front of the restore).
+  // LAST in the table: save_residents / restore_residents pair blocks by their order
+  b.add(sg_acc, G_STRUCT, Dim::Cap, 1, 0, Z, never, res);
 }
 
 size_t Buffers::count(const Buf &b, const Engine &e) const {

@@ -433,6 +433,21 @@ int rxmd_hip_bonds_vjp_device(rxmd_handle h, int flags, double bo_min, long long
   return guarded(h, [&](Engine &e) { e.bonds_vjp_device(flags, bo_min, E, grad_bo, grad_bo3, grad_vec3, grad_pos3, static_cast<hipStream_t>(stream)); });
 }
 
+// ---- structure statistics accumulated on the device (structure.hip) ----
+int rxmd_hip_structure_begin(rxmd_handle h, double r_max, int nbins_r, int nshells, const double *angle_cut, int nbins_angle) {
+  return guarded(h, [&](Engine &e) { e.structure_begin(r_max, nbins_r, nshells, angle_cut, nbins_angle); });
+}
+int rxmd_hip_structure_sample(rxmd_handle h) {
+  return guarded(h, [&](Engine &e) { e.structure_sample(); });
+}
+int rxmd_hip_structure_get(rxmd_handle h, long long *pair_counts, long long pair_capacity, long long *angle_counts, long long angle_capacity,
+                           long long *atoms_per_type, double *volume_sum, long long *frames) {
+  return guarded(h, [&](Engine &e) { e.structure_get(pair_counts, pair_capacity, angle_counts, angle_capacity, atoms_per_type, volume_sum, frames); });
+}
+int rxmd_hip_structure_end(rxmd_handle h) {
+  return guarded(h, [&](Engine &e) { e.structure_end(); });
+}
+
 // ---- introspection ----
 int rxmd_hip_get_stats(rxmd_handle h, rxmd_stats *out) {
   if (!out) return RXMD_E_ARG;

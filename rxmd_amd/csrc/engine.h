@@ -209,7 +209,7 @@ enum class Dim : unsigned char { Fixed, NB, Rows10, List10, Cap };   // what a b
 enum class Refill : unsigned char { Never, Whole, Ghosts };          // RXMD_POISON_ALLOC refill before a rebuild: none, the whole buffer, elements [N, NB)
 enum class Space : unsigned char { Device, Pinned, PinnedCoherent };
 // re-allocation groups.  Those before G_ON_DEMAND exist from set-up on (Buffers::alloc_setup); the others are allocated when first needed
-enum { G_SETUP, G_BOND, G_WIN, G_CELLSTART, G_LIST10, G_PARTIALS, G_ON_DEMAND, G_CUBTMP = G_ON_DEMAND, G_FFBLOB, G_PQBLOB, G_E4B, G_SEG, G_SEG_PINNED, G_XBUF, G_DH_SERVE, G_BGRAPH, G_BVJP, G_PGRAPH, G_COUNT };
+enum { G_SETUP, G_BOND, G_WIN, G_CELLSTART, G_LIST10, G_PARTIALS, G_ON_DEMAND, G_CUBTMP = G_ON_DEMAND, G_FFBLOB, G_PQBLOB, G_E4B, G_SEG, G_SEG_PINNED, G_XBUF, G_DH_SERVE, G_BGRAPH, G_BVJP, G_PGRAPH, G_STRUCT, G_COUNT };
 enum : unsigned { BUF_PQEQ = 1u, BUF_RESIDENT = 2u, BUF_QEQ_F32 = 4u };   // exists only with PQEq ; resident state that grow_capacity carries over ; exists only while the fp32 matrix stream is requested (set_qeq_precision)
 struct Buf { void **pp; size_t elem; int group; Dim dim; size_t mul, add_; Fill fill; Refill refill; unsigned flags; Space space; size_t bytes; };   // bytes: what was allocated (0: nothing of ours)
 struct Buffers {
@@ -251,7 +251,7 @@ struct StreamSwap {                                   // the engine's stream aga
 };
 
 struct ScaleArgs;
-struct PairList;                         // what the kernels of pair_graph.hip need to walk a row of the 10 A list
+struct PairList;                         // what the kernels of pair_graph.hip and structure.hip need to walk a row of the 10 A list (pair_walk.h)
 struct WinPassArgs; struct RowPassArgs;   // the operands of the two matrix-pass kernels (spmv_kernels.h)
 struct Engine {
   const Options opt = Options::from_env();   // the environment switches of this engine (options.def), read once at create
@@ -440,6 +440,16 @@ struct Engine {
   long long select_pairs(double r_cut);            // pg_cnt / pg_off for this cut-off -> the number selected (the one host wait of the call)
   PairList pair_list(double r_cut) const;
   long long *pg_cnt = nullptr, *pg_off = nullptr; int pg_rows = 0;
+  // rxmd_hip_structure_* (structure.hip): int64 accumulators of the structure statistics in one block sg_acc = pair counts [nso][nso][nbins_r], angle
+  // counts [nshells][nso][nso][nso][nbins_angle], residents per type [nso]; allocated by structure_begin, resident state (grow_capacity carries it
+  // over), freed by structure_end.  The volume sum and the frame count stay on the host: the lattice is host state
+  void structure_begin(double r_max, int nbins_r, int nshells, const double *angle_cut, int nbins_angle);
+  void structure_sample();                         // the state of the last list build into the accumulators, on `stream`; no host wait beyond finish_force
+  void structure_get(long long *pair_counts, long long pair_capacity, long long *angle_counts, long long angle_capacity, long long *atoms_per_type, double *volume_sum, long long *frames);
+  void structure_end();
+  long long *sg_acc = nullptr; bool sg_on = false;
+  double sg_rmax = 0, sg_cut[4] = {0, 0, 0, 0}, sg_volume = 0; int sg_nbr = 0, sg_nsh = 0, sg_nba = 0;
+  size_t sg_npair = 0, sg_nangle = 0; long long sg_frames = 0;
   void build_ghosts_and_lists(bool qeq_prepass = false);   // COPYATOMS(MODE_COPY) + LINKEDLIST + NEIGHBORLIST + 10 A list/hessian, once per step
   void qeq_start_vectors();        // qs, qt, hs, ht of qeq.F90:36-63 and their cell-sorted copy (before the list sweep that uses them)
   int *rows_int = nullptr, *rows_bnd = nullptr; int n_bnd = 0; bool rows_split_pending = false;   // interior / boundary rows (multi-rank)

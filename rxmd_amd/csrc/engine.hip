@@ -768,6 +768,7 @@ void Engine::grow_capacity(int new_nb) {
   NB = new_nb;
   alloc_device();
   upload_ff();
+  if (sg_on) bufs.alloc_group(*this, G_STRUCT, sg_npair + sg_nangle + static_cast<size_t>(ff.nso));   // the structure accumulators are resident state (structure.hip)
   bufs.restore_residents(kept);
   G = N;
 }

@@ -11,10 +11,10 @@
 //   k_pair_fill    the same walk; an entry's output index = off[i] + selected entries of the batches before + its rank among the set bits of its
 //                  batch's ballot below its lane: list order kept, no atomics, the selected entries of a batch are stored to consecutive addresses.
 //                  It decodes and gathers again: a 64-bit mask per batch kept by the count spared the fill 6-8 % and cost a buffer (NOTES.md)
-// The two routes from an entry to k are those of k_ehb_sweep (bonded.hip): the 4-byte entry where this build wrote the stream (nb10_valid), else
-// the 2-byte window slot: sl10 & 0x7fff -> win_k of the row's group (rpos[i] / WIN_ROWS) -> first position of the slot's unit + offset in the unit.
+// The row walk (PairList, pair_partner_pos: the two routes from an entry to k) is pair_walk.h, shared with structure.hip.
 // Algorithmic bytes per LIST entry, count: 4 (entry) or 2 (slot) streamed + 4 (perm) + 24 (position) gathered; fill: the same again, + 8 for hval,
 // and per SELECTED entry 16 out (src, dst) + 24 (vec3) + 12 (shift3) + 8 (hval), + 4 or 8 gathered for a ghost's owner or a global id.
+#include "pair_walk.h"
 #include "scan.h"
 
 #include <cmath>
@@ -23,26 +23,6 @@
 namespace rxmd {
 
 constexpr int PG_ROWS = 4;                       // rows (wavefronts) of a workgroup
-
-struct PairList {                                // what both kernels need to walk a row; by value
-  int N, G, S10, slots, byplace;                 // slots: decode through the window slots (no 4-byte entries in this build)
-  double rcut;                                   // <= 0: every entry
-  const int *n10, *nb10, *rpos, *win_k, *perm;
-  const unsigned short *sl10;
-  const double *x, *y, *z;
-};
-
-// cell-sorted position of entry kk of the row whose streams start at `row` (wk: the window of the row's group, slot route only); clamped into
-// [0, G) as the slot route of k_ehb_sweep is, so that a damaged stream cannot send the gathers behind it out of the arrays
-__device__ inline int pair_partner_pos(const PairList &L, size_t row, const int *__restrict__ wk, int kk) {
-  int k;
-  if (L.slots) {
-    const int sl = L.sl10[row + kk] & 0x7fff;
-    k = wk[min(sl / WIN_UNIT, WIN_MAXUNITS - 1)] + (sl & (WIN_UNIT - 1));
-  } else
-    k = static_cast<int>(static_cast<unsigned>(L.nb10[row + kk]) & NB10_IDX_MASK);
-  return min(max(k, 0), L.G - 1);
-}
 
 __global__ void __launch_bounds__(64 * PG_ROWS) k_pair_count(PairList L, long long *__restrict__ cnt) {
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));

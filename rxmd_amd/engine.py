@@ -279,6 +279,52 @@ class RxmdEngine:
         -> E, the number of directed pairs selected; nothing is written when capacity < E"""
         return self._chk(self.L.rxmd_hip_get_pairs_device(self.h, PAIRS_GID if as_gid else 0, float(r_cut), int(capacity), *map(_addr, (src_ptr, dst_ptr, shift_ptr, vec_ptr, h_ptr)), _addr(stream)))
 
+    # ---- structure statistics accumulated on the device (include/rxmd_hip.h: rxmd_hip_structure_*; normalisation: rxmd_amd/structure.py) ----
+    def _nso(self):
+        """the ffield's number of atom types: the extent of the count arrays"""
+        if getattr(self, "_nso_cached", None) is None:
+            out = np.zeros(4096)
+            was = self.L.rxmd_host_ffield_lg(int(self.cfg.lg))
+            try:
+                rc = self.L.rxmd_host_ffield_table(self._ff, None, 6, _ptr(out), len(out))
+            finally:
+                self.L.rxmd_host_ffield_lg(was)
+            if rc < 0:
+                raise RxmdError(rc, "cannot parse %s" % self._ff.decode())
+            self._nso_cached = int(out[0])
+        return self._nso_cached
+
+    def structure_begin(self, r_max, nbins_r, angle_cuts=(), nbins_angle=180):
+        """zeroed accumulators on the device: pair counts in nbins_r bins up to r_max (<= the reach of the 10 A list), bond-angle counts in
+        nbins_angle bins up to 180 degrees for every shell of angle_cuts (ascending, at most four, each <= r_max; empty: no angles).
+        Calling it again starts from zero."""
+        cuts = np.ascontiguousarray(angle_cuts, np.float64).reshape(-1)
+        self._chk(self.L.rxmd_hip_structure_begin(self.h, float(r_max), int(nbins_r), len(cuts), _ptr(cuts) if len(cuts) else None, int(nbins_angle)))
+        self._structure = (float(r_max), int(nbins_r), [float(c) for c in cuts], int(nbins_angle) if len(cuts) else 0)
+
+    def structure_sample(self):
+        """add the state of the last QEq / FORCE / step to the accumulators (RxmdError -7 without structure_begin or without a valid 10 A list)"""
+        self._chk(self.L.rxmd_hip_structure_sample(self.h))
+
+    def structure_counts(self):
+        """-> dict: pair_counts int64 [nso, nso, nbins_r] (resident type, partner type, r bin; directed), angle_counts int64 [nshells, nso, nso, nso,
+        nbins_angle] (shell, end type, centre type, end type, angle bin; twice the reference's table), atoms_per_type int64 [nso], volume_sum
+        [A^3], frames -- the sums over every sample so far, of THIS rank (structure.merge sums ranks) -- and the binning (r_max, angle_cuts).
+        Does not reset."""
+        if getattr(self, "_structure", None) is None:
+            raise RxmdError(-7, "structure_counts: call structure_begin first")
+        r_max, nbr, cuts, nba = self._structure
+        nso = self._nso()
+        pair = np.zeros((nso, nso, nbr), np.int64); ang = np.zeros((len(cuts), nso, nso, nso, nba), np.int64); npt = np.zeros(nso, np.int64)
+        vol = C.c_double(0); fr = C.c_longlong(0)
+        self._chk(self.L.rxmd_hip_structure_get(self.h, _ptr(pair), pair.size, _ptr(ang) if ang.size else None, ang.size, _ptr(npt), C.byref(vol), C.byref(fr)))
+        return dict(pair_counts=pair, angle_counts=ang, atoms_per_type=npt, volume_sum=vol.value, frames=fr.value, r_max=r_max, angle_cuts=list(cuts))
+
+    def structure_end(self):
+        """free the accumulators"""
+        self._chk(self.L.rxmd_hip_structure_end(self.h))
+        self._structure = None
+
     # ---- introspection ----
     def stats(self):
         s = RxmdStats(); self._chk(self.L.rxmd_hip_get_stats(self.h, C.byref(s))); return s.asdict()
