@@ -1,7 +1,7 @@
 """real window pass / row pass: back to back (debug tap 104) against the same kernels inside the CG loop of MD steps"""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests")); sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from test_gpu_parity import _engine
+from parity import _engine
 e = _engine("rdx168", (18, 18, 18), qeq_mode=1)
 e.QEq(); e.FORCE()
 def loop(tag, nsteps=4):

@@ -4,7 +4,7 @@ import os, sys, subprocess
 here = os.path.dirname(os.path.abspath(__file__)); root = os.path.join(here, "..")
 if len(sys.argv) > 1 and sys.argv[1] == "--child":
     sys.path.insert(0, os.path.join(root, "tests")); sys.path.insert(0, root)
-    from test_gpu_parity import _engine
+    from parity import _engine
     e = _engine("rdx168", (18, 18, 18), qeq_mode=1)
     e.QEq(); e.FORCE()
     os.environ["RXMD_ISO_REPS"] = "50"; os.environ["RXMD_ISO_COPIES"] = "1"

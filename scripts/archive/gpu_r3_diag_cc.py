@@ -3,7 +3,7 @@ import sys, os
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests")); sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np
 import oracle_api as oa
-from test_gpu_parity import _engine, _oracle
+from parity import _engine, _oracle
 kw = dict(QEq_tol=1e-12, NMAXQEq=2000)
 for case, mc in (("rdx222", (2, 2, 2)), ("rdx168", (3, 3, 3))):
     o = _oracle(case, mc, **kw); o.qeq(); o.force()

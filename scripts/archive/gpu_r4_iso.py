@@ -2,7 +2,7 @@
 requested before the barrier / default again"""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests")); sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from test_gpu_parity import _engine
+from parity import _engine
 e = _engine("rdx168", (18, 18, 18), qeq_mode=1)
 e.QEq(); e.FORCE(); e.step(2)
 os.environ["RXMD_ISO_REPS"] = "100"

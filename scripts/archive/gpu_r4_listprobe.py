@@ -1,7 +1,7 @@
 """k_list10 with single stores switched off (experiments library, RXMD_LIST_PROBE bits 4 / 8 / 16: no slot / entry / value store): where is its time?"""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests")); sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from test_gpu_parity import _engine
+from parity import _engine
 for probe in ("0", "4", "8", "16", "28"):
     os.environ["RXMD_LIST_PROBE"] = probe
     os.environ["RXMD_SPMV_WIN"] = "0"; os.environ["RXMD_NONBOND_WIN"] = "0"

@@ -1,7 +1,7 @@
 """stripped-down forms of the matrix pass, timed in isolation (debug tap 102): streams only / + gathers / + ghost sums and reductions / + tail"""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests")); sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from test_gpu_parity import _engine
+from parity import _engine
 for case, mc in (("rdx168", (18, 18, 18)), ("ice644", (60, 35, 40))):
     e = _engine(case, mc, qeq_mode=1)
     e.QEq(); e.FORCE()

@@ -64,18 +64,6 @@ def oracle(name, shift=0.0, with_v=False, **kw):
     return oa.Oracle(ff, lat2, ranks, v0=[v] if with_v else None, **kw)
 
 
-def rec10(ranks, v=None):
-    """the rxff record block of one rank: rnorm, v, q = 0, type + gid * 1e-13"""
-    r = ranks[0]
-    n = len(r["type"])
-    rec = np.zeros((n, 10))
-    rec[:, 0:3] = r["rnorm"]
-    if v is not None:
-        rec[:, 3:6] = v
-    rec[:, 7] = r["type"] + r["gid"] * 1e-13
-    return rec
-
-
 def regime(o):
     """what the gates read, from an oracle whose lists are built (after qeq() and force())"""
     n = len(o.gids())

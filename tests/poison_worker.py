@@ -6,7 +6,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE); sys.path.insert(0, os.path.dirname(HERE))
 import oracle_api as oa
-from test_gpu_parity import _engine, _oracle, q_err, f_err, e_err
+from parity import _engine, _oracle, q_err, f_err, e_err, lattice_sequence
 
 assert os.environ.get("RXMD_POISON_ALLOC") == "1"
 kw = dict(QEq_tol=1e-12, NMAXQEq=2000)
@@ -68,9 +68,8 @@ gate_run("(a) rdx222 bond tables from 1024", e, refs["rdx222"], 3, False)
 assert e.stats()["nbonds"] > 1024
 e.close()
 
-# (b) set_lattice: the grid-sized buffers are re-allocated at the expansion, every per-atom buffer at the compression (lattice_sequence of
-# test_gpu_variable_cell_oracle.py); the oracle follows through its own set_lattice and the same steps
-from test_gpu_variable_cell_oracle import lattice_sequence
+# (b) set_lattice: the grid-sized buffers are re-allocated at the expansion, every per-atom buffer at the compression (parity.lattice_sequence);
+# the oracle follows through its own set_lattice and the same steps
 o = _oracle("rdx222", (2, 2, 2), **kw)
 e = _engine("rdx222", (2, 2, 2), **kw)
 seq = dict(lattice_sequence(list(e.lattice), e.cutoffs()[1]))

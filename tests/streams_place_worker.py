@@ -5,7 +5,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE); sys.path.insert(0, os.path.dirname(HERE))
 import pytest
-from test_gpu_streams_by_place import perturbed_rdx, run
+from parity import perturbed_rdx, run
 
 assert os.environ.get("RXMD_POISON_ALLOC") == "1"
 mp = pytest.MonkeyPatch()

@@ -1,33 +1,20 @@
 """world_size-2/3 gloo tests of the N>1 plumbing on CPU: the transport callbacks the engine drives its six-stage
 exchange with (C-ABI contract checked by rxmd_host_comm_selftest with host buffers), and the domain decomposition."""
 import os
-import socket
 import numpy as np
 import pytest
-import torch.multiprocessing as mp
 
 import oracle_api as oa
 from rxmd_amd import system
 import mr_worker
-
-
-def _port():
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
+from ranks import run_ranks
 
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_transport_contract_over_gloo(world):
-    ctx = mp.get_context("spawn")
-    with ctx.Manager() as m:
-        out = m.dict()
-        port = _port()
-        ps = [ctx.Process(target=mr_worker.transport_selftest, args=(r, world, port, out)) for r in range(world)]
-        [p.start() for p in ps]; [p.join(120) for p in ps]
-        assert len(out) == world
-        for r in range(world):
-            rc, nex, nar, err = out[r]
-            assert rc == 0, (r, rc, err)
-            assert nex == 6 and nar == 1
+    for r, (rc, nex, nar, err) in enumerate(run_ranks(mr_worker.transport_selftest, world, timeout=120, gpu=False)):
+        assert rc == 0, (r, rc, err)
+        assert nex == 6 and nar == 1
 
 
 def test_domain_decomposition_matches_reference_rank_grid():

@@ -10,14 +10,10 @@ import numpy as np
 import pytest
 
 import oracle_api as oa
+from parity import q_err
 
 KW = dict(QEq_tol=1e-12, NMAXQEq=2000)
 CASES = [("rdx168", (1, 1, 1)), ("ice644", (6, 4, 4))]
-
-
-def q_err(q, qref):                                 # the parity metric of tests/test_gpu_parity.py
-    qrms = np.sqrt((qref ** 2).mean())
-    return (np.abs(q - qref) / np.maximum(np.abs(qref), max(qrms, 1e-300))).max()
 
 
 def fixture(case):

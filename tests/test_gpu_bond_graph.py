@@ -2,7 +2,7 @@
 coordinate arrays in device memory.
 
 The yardstick is the host path of the SAME engine in the SAME state: RxmdEngine.bonds() + atoms()["gid"], which is held to the oracle per slot
-(test_gpu_parity.check_bond_order_taps / compare_bond_order_taps) and to the reference's .bnd file (test_gpu_output.py).  Both paths copy the same
+(test_gpu_parity.check_bond_order_taps / parity.compare_bond_order_taps) and to the reference's .bnd file (test_gpu_output.py).  Both paths copy the same
 stored doubles and the same global ids, so every comparison with it is exact (np.array_equal).
 
 Bounds that are not exact, and where they come from:
@@ -17,49 +17,11 @@ import pytest
 import torch
 
 import oracle_api as oa
-import offlattice_systems as ol
 from npt_reference import hmat
-from test_gpu_parity import _engine
+from parity import _engine, code as _code
+from graph_support import _offlattice_engine, _host_coo, _device_coo, _ref, _model, _dev, DEV, EPS, SENT_I, SENT_F, KW5
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-EPS = np.finfo(np.float64).eps
-SENT_I, SENT_F = -777, -777.25                    # what the output buffers hold before a call
-KW5 = dict(QEq_tol=1e-300, NMAXQEq=5)             # the off-lattice boxes: five fixed CG iterations, as test_gpu_offlattice runs them (bonds need no charges)
-
-
-def _offlattice_engine(name, **kw):
-    import rxmd_amd
-    ff, lat2, ranks, v = ol.build(name)
-    e = rxmd_amd.RxmdEngine(ff, lat2, **kw)
-    e.set_atoms_rxff(ol.rec10(ranks))
-    return e
-
-
-def _host_coo(e, bo_min=None):
-    """the host path flattened row-major: (atoms, src gid, dst gid, bo)"""
-    a = e.atoms()
-    cnt, pg, bo = e.bonds()
-    mask = np.arange(pg.shape[1])[None, :] < cnt[:, None]
-    src, dst, b = np.repeat(a["gid"], cnt), pg[mask], bo[mask]
-    if bo_min is not None:
-        keep = b >= bo_min
-        src, dst, b = src[keep], dst[keep], b[keep]
-    return a, src, dst, b
-
-
-def _device_coo(e, bo_min=0.0, as_gid=False, capacity=None):
-    """count, then fill sentinel-filled torch tensors of `capacity` (default: exactly E) -> (E, src, dst, bo, parts [.,3], vec [.,3]) as numpy"""
-    E = e.bonds_device(0, 0, 0, 0, bo_min=bo_min, as_gid=as_gid)
-    cap = E if capacity is None else capacity
-    src = torch.full((cap,), SENT_I, dtype=torch.int64, device=DEV); dst = torch.full_like(src, SENT_I)
-    bo = torch.full((cap,), SENT_F, dtype=torch.float64, device=DEV)
-    parts = torch.full((cap, 3), SENT_F, dtype=torch.float64, device=DEV); vec = torch.full_like(parts, SENT_F)
-    got = e.bonds_device(cap, src.data_ptr(), dst.data_ptr(), bo.data_ptr(), bo3_ptr=parts.data_ptr(), vec_ptr=vec.data_ptr(), bo_min=bo_min, as_gid=as_gid,
-                         stream=torch.cuda.current_stream().cuda_stream)
-    assert got == E, (got, E)
-    return E, src.cpu().numpy(), dst.cpu().numpy(), bo.cpu().numpy(), parts.cpu().numpy(), vec.cpu().numpy()
 
 
 def _check_gid_mode(e, label):
@@ -175,11 +137,6 @@ def test_scratch_follows_the_growth_of_the_bond_tables(monkeypatch):
 
 
 # ---- 6. capacity and refusals ------------------------------------------------------------------------------------------------------------
-def _code(call):
-    import rxmd_amd
-    with pytest.raises(rxmd_amd.RxmdError) as ei:
-        call()
-    return ei.value.code
 
 
 def test_capacity_and_refusals():
@@ -219,7 +176,6 @@ def test_capacity_and_refusals():
 # ---- 7. torch ----------------------------------------------------------------------------------------------------------------------------
 def _torch_case(shift):
     """rdx168 handed over in a random permutation (gid = the original ids), optionally every atom moved by a lattice vector"""
-    from test_gpu_device_eval import _ref, _model, _dev
     r = _ref("rdx168", (1, 1, 1))
     n = len(r["pos"])
     rng = np.random.default_rng(20250211)

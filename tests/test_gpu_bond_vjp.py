@@ -27,8 +27,8 @@ import torch
 
 import oracle_api as oa
 import offlattice_systems as ol
-from test_gpu_parity import _engine
-from test_gpu_bond_graph import _device_coo, _offlattice_engine, _code
+from parity import _engine, code as _code
+from graph_support import _device_coo, _offlattice_engine
 
 pytestmark = pytest.mark.gpu
 

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import oracle_api as oa
-from test_gpu_parity import FTOL, ETOL, f_err, e_err
+from parity import FTOL, ETOL, f_err, e_err
 
 pytestmark = pytest.mark.gpu
 

@@ -13,42 +13,10 @@ import torch
 
 import oracle_api as oa
 from npt_reference import hmat
-from test_gpu_parity import _engine, _oracle, q_err, f_err, e_err, QTOL, FTOL, ETOL
+from parity import _engine, q_err, f_err, e_err, QTOL, FTOL, ETOL
+from graph_support import _ref, _model, _dev, TIGHT, DEV, EPS
 
 pytestmark = pytest.mark.gpu
-
-TIGHT = dict(QEq_tol=1e-12, NMAXQEq=2000)
-DEV = "cuda:0"
-EPS = np.finfo(np.float64).eps
-
-_REF = {}
-
-
-def _lattice(case, mc):
-    lat = oa.make_system(case)[3]
-    return [lat[0] * mc[0], lat[1] * mc[1], lat[2] * mc[2]] + list(lat[3:6])
-
-
-def _ref(case, mc):
-    """the oracle at tight tolerance, once per system: positions, types, gids, charges, forces, energies, virial (arrays are read-only)"""
-    if case not in _REF:
-        o = _oracle(case, mc, **TIGHT); o.qeq(); o.force()
-        r = dict(pos=o.pos().copy(), type=o.types().copy(), gid=o.gids().copy(), q=o.charges().copy(), f=o.forces().copy(), pe=o.energy().copy(),
-                 astr=o.astr(reset=True).copy(), lat=_lattice(case, mc), ff=oa.make_system(case)[0])
-        for v in r.values():
-            if isinstance(v, np.ndarray):
-                v.setflags(write=False)
-        _REF[case] = r
-    return _REF[case]
-
-
-def _model(r, **kw):
-    from rxmd_amd.torch_front import ReaxFF
-    return ReaxFF(r["ff"], r["lat"], r["type"], gid=r["gid"], **kw)
-
-
-def _dev(a):
-    return torch.tensor(np.asarray(a), dtype=torch.float64, device=DEV)
 
 
 def _arrays_run(r, pos, natoms=None, typ=None, gid=None, **kw):

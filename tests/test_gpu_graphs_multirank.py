@@ -5,7 +5,7 @@ test_gpu_bond_graph.py): global ids and positions of ghosts that came from anoth
 rows split into an interior and a boundary launch, a rank with no atom, the list of a QEq-only build, PQEq's longer list, a skewed cell.
 
 Systems (the smallest that still decompose): rdx222 = RDX 2 x 2 x 2, 1,344 atoms, on both grids; the same with every atom displaced by N(0, 0.05 A)
-(seed 2048) and velocities by global id (mr_worker.mode_velocities, seed 7, sigma 0.05 as test_gpu_scale), three steps; mr_worker.slab_system (rank 1
+(seed 2048) and velocities by global id (parity.mode_velocities, seed 7, sigma 0.05 as test_gpu_scale), three steps; parity.slab_system (rank 1
 owns nothing); the SiC nanoparticle with PQEq, one particle per rank; triclinic MoS2 3 x 3 x 2; rdx222 with the fp32 matrix stream.  Seed 2048 was
 picked on the CPU: the brute-force distances of the starting state keep 2.7e-5 / 1.0e-5 / 7.8e-7 A from 3.0 / 6.5 / 9.5 A, and on the multi-rank oracle 2 atoms
 (2 x 1 x 1) and 3 atoms (2 x 2 x 2) change rank within the three steps -- seeds 2027..2032 with the same velocities move none at this size.
@@ -24,7 +24,7 @@ Bounds, and where they come from:
   * row counts of the whole list: equal to debug tap 6 and to tap 104 of the multi-rank oracle, rank by rank.
   * math.fsum row sums of hval against debug tap 7 and oracle tap 108: rtol 1e-12 (test_gpu_parity.py:81).  With the fp32 stream every value is one
     float rounding (relative 2^-24) from the oracle's double and all values of a row have one sign: rtol 2^-24 + 1e-12 against tap 108 there.
-  * hval entry by entry: test_gpu_pair_graph.check_hval_entries, 8 eps |h|, at most 2 entries matched at the neighbouring float; fp32 stream: exact.
+  * hval entry by entry: graph_support.check_hval_entries, 8 eps |h|, at most 2 entries matched at the neighbouring float; fp32 stream: exact.
     One of the four forms of the reference must hold ALL ranks of a system (one kernel build), and the 2 entries are counted over all its ranks.
     PQEq: row sums only.  MoS2: in a skewed box a ghost beyond the reference's QEq ghost shell is in the list but not in the QEq matrix (lists.hip: inq)
     and would be exported as 0; in this box at 2 x 1 x 1 no partner is such a ghost (none of the 239,112 entries is 0), so every entry is held to the
@@ -42,16 +42,16 @@ Bounds, and where they come from:
 import json
 import math
 import os
-import socket
 
 import numpy as np
 import pytest
-import torch.multiprocessing as mp
 
 import oracle_api as oa
 import graph_worker
+from ranks import run_ranks
 from npt_reference import hmat
-from test_gpu_pair_graph import brute_force, _select, check_hval_entries, qeq_table, CUTS, EDGES, SENT_I, SENT_F, TIGHT
+from parity import build_system
+from graph_support import brute_force, _select, check_hval_entries, qeq_table, CUTS, EDGES, SENT_I, SENT_F, TIGHT
 
 pytestmark = pytest.mark.gpu
 
@@ -76,10 +76,6 @@ assert COUNTS["rdx222"] == (13776, 157408, 491904)
 CUTS_AFTER = tuple(6.5 + 1e-3 * k for k in range(5))   # after the steps: the first of these with no distance within 1e-8 A
 
 
-def _port():
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
-
-
 def _cuts(spec):
     return CUTS + ((12.0,) if spec.get("pqeq") else ()) + (0.0,)
 
@@ -93,25 +89,13 @@ def _run(name, tmp_path):
     spec = dict(SYSTEMS[name], kw=TIGHT, dir=str(tmp_path))
     spec["cuts"] = _cuts(spec); spec["cuts_after"] = CUTS_AFTER
     vp = spec["vp"]; world = vp[0] * vp[1] * vp[2]
-    ctx = mp.get_context("spawn")
-    with ctx.Manager() as m:
-        out = m.dict()
-        port = _port()
-        ps = [ctx.Process(target=graph_worker.graph_rank, args=(r, world, port, spec, out)) for r in range(world)]
-        [p.start() for p in ps]; [p.join(600) for p in ps]
-        for p in ps:
-            if p.is_alive():
-                p.kill()
-        assert len(out) == world, "a rank died or hung"
-        res = [out[r] for r in range(world)]
-    for o in res:
-        assert "error" not in o, o.get("error")
+    run_ranks(graph_worker.graph_rank, world, spec, timeout=600)
     ranks = []
     for r in range(world):
         with np.load(os.path.join(str(tmp_path), "rank%d.npz" % r)) as f:
             ranks.append({k: f[k] for k in f.files})
         assert str(ranks[r]["transport_error"]) == "None" and (ranks[r]["transport"] > 0).all()
-    ff, lat, recs, vs = graph_worker.build_system(spec)
+    ff, lat, recs, vs = build_system(spec)
     return dict(name=name, spec=spec, ff=ff, lat=lat, recs=recs, ranks=ranks, world=world)
 
 

@@ -3,19 +3,15 @@ forces depend on the decomposition, so N-rank results are compared with the MPI 
 All ranks share the single GPU of the test box; messages travel host-staged over gloo, so this exercises the engine's
 staged exchange (ghost build, vector halos, force return, migration, all-reduces) exactly as the RCCL transport does."""
 import os
-import socket
 import numpy as np
 import pytest
-import torch.multiprocessing as mp
 
 import oracle_api as oa
 import mr_worker
+from ranks import run_ranks
+from parity import _engine, _oracle, q_err, f_err, slab_system
 
 pytestmark = pytest.mark.gpu
-
-
-def _port():
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
 
 
 @pytest.mark.parametrize("case,steps,win", [("rdx222_v211_tight", 0, "1"), ("rdx222_v222_tight", 0, "1"), ("rdx222_v222_md3", 3, "1"), ("rdx222_v222_md3", 3, "0"),
@@ -28,22 +24,13 @@ def test_vprocs_parity_vs_mpi_reference(case, steps, win, monkeypatch):
     monkeypatch.setenv("RXMD_SPMV_WIN", win)
     g = np.load(os.path.join(oa.GOLD, case + ".npz"))
     vp = tuple(int(x) for x in g["vprocs"]); world = vp[0] * vp[1] * vp[2]
-    ctx = mp.get_context("spawn")
-    with ctx.Manager() as m:
-        out = m.dict()
-        port = _port()
-        ps = [ctx.Process(target=mr_worker.engine_rank, args=(r, world, port, case, vp, steps, out)) for r in range(world)]
-        [p.start() for p in ps]; [p.join(600) for p in ps]
-        assert len(out) == world, "a rank died"
-        res = [out[r] for r in range(world)]
+    res = run_ranks(mr_worker.engine_rank, world, case, vp, steps, timeout=600)
     for r, o in enumerate(res):
-        assert "error" not in o, o.get("error")
         assert o["err"] == "None"
         assert np.array_equal(o["gid"], g["gid_%d" % r])
         qref, fref = g["charge_%d" % r], g["force_%d" % r]
-        qrms = np.sqrt((qref ** 2).mean()); frms = np.sqrt((fref ** 2).mean())
-        assert (np.abs(o["q"] - qref) / np.maximum(np.abs(qref), qrms)).max() <= 1e-6
-        assert (np.abs(o["f"] - fref).max(axis=1) / np.maximum(np.abs(fref).max(axis=1), frms)).max() <= (1e-6 if steps == 0 else 1e-5)
+        assert q_err(o["q"], qref) <= 1e-6
+        assert f_err(o["f"], fref) <= (1e-6 if steps == 0 else 1e-5)
         assert np.abs(o["pos"] - g["pos_%d" % r]).max() <= 1e-8
         # the exit iteration moves with the summation order (the reference itself goes 35 -> 31..39 under atom
         # re-ordering): same neighbourhood, not the same count; charges and forces above are the gate
@@ -91,24 +78,12 @@ def test_native_rccl_with_real_peers_vs_mpi_reference(case, steps, qeq_mode):
         pytest.skip("needs two GPUs: the RCCL peer-to-peer path cannot run with both ranks on one device")
     g = np.load(os.path.join(oa.GOLD, case + ".npz"))
     vp = tuple(int(x) for x in g["vprocs"]); world = 2
-    ctx = mp.get_context("spawn")
-    with ctx.Manager() as m:
-        out = m.dict()
-        port = _port()
-        ps = [ctx.Process(target=mr_worker.engine_rank_rccl, args=(r, world, port, case, vp, steps, qeq_mode, out)) for r in range(world)]
-        [p.start() for p in ps]; [p.join(900) for p in ps]
-        for p in ps:
-            if p.is_alive():
-                p.kill()
-        assert len(out) == world, "a rank died or hung"
-        res = [out[r] for r in range(world)]
+    res = run_ranks(mr_worker.engine_rank_rccl, world, case, vp, steps, qeq_mode, timeout=900)
     for r, o in enumerate(res):
-        assert "error" not in o, o.get("error")
         assert np.array_equal(o["gid"], g["gid_%d" % r])
         qref, fref = g["charge_%d" % r], g["force_%d" % r]
-        qrms = np.sqrt((qref ** 2).mean()); frms = np.sqrt((fref ** 2).mean())
-        assert (np.abs(o["q"] - qref) / np.maximum(np.abs(qref), qrms)).max() <= 1e-6
-        assert (np.abs(o["f"] - fref).max(axis=1) / np.maximum(np.abs(fref).max(axis=1), frms)).max() <= (1e-6 if steps == 0 else 1e-5)
+        assert q_err(o["q"], qref) <= 1e-6
+        assert f_err(o["f"], fref) <= (1e-6 if steps == 0 else 1e-5)
         assert np.abs(o["pos"] - g["pos_%d" % r]).max() <= 1e-8
         assert o["nghost"] > 0
 
@@ -117,28 +92,19 @@ def test_native_rccl_with_real_peers_vs_mpi_reference(case, steps, qeq_mode):
 def test_a_rank_that_owns_no_atom(qeq_mode):
     """ragged decomposition: all 168 atoms in the lower half of the box, rank 1 of 2x1x1 is EMPTY (zero residents, ghosts only) and must
     still answer every exchange round and all-reduce; compared per rank with the multi-rank oracle, energies with the global sums"""
-    ff, names, frac, lat = mr_worker.slab_system()
+    ff, names, frac, lat = slab_system()
     lat_s, ranks = oa.geninit(names, frac, lat, oa.ffield_names(ff), vprocs=(2, 1, 1))
     assert [len(r["type"]) for r in ranks] == [168, 0]
     o = oa.Oracle(ff, lat_s, ranks, vprocs=(2, 1, 1), QEq_tol=1e-12, NMAXQEq=2000, nbuffer=20000)
     o.qeq(); o.force(); pe_ref = o.energy()
-    ctx = mp.get_context("spawn")
-    with ctx.Manager() as m:
-        out = m.dict()
-        port = _port()
-        ps = [ctx.Process(target=mr_worker.engine_rank_empty, args=(r, 2, port, 0, qeq_mode, out)) for r in range(2)]
-        [p.start() for p in ps]; [p.join(600) for p in ps]
-        assert len(out) == 2, "a rank died"
-        res = [out[r] for r in range(2)]
+    res = run_ranks(mr_worker.engine_rank_empty, 2, 0, qeq_mode, timeout=600)
     for r, x in enumerate(res):
-        assert "error" not in x, x.get("error")
         assert x["err"] == "None"
     assert res[0]["n0"] == 168 and res[1]["n0"] == 0 and len(res[1]["gid"]) == 0
     assert np.array_equal(res[0]["gid"], o.gids(0))
     qref, fref = o.charges(0), o.forces(0)
-    qrms = np.sqrt((qref ** 2).mean()); frms = np.sqrt((fref ** 2).mean())
-    assert (np.abs(res[0]["q"] - qref) / np.maximum(np.abs(qref), qrms)).max() <= 1e-6
-    assert (np.abs(res[0]["f"] - fref).max(axis=1) / np.maximum(np.abs(fref).max(axis=1), frms)).max() <= 1e-6
+    assert q_err(res[0]["q"], qref) <= 1e-6
+    assert f_err(res[0]["f"], fref) <= 1e-6
     pe = np.array(res[0]["pe"]) + np.array(res[1]["pe"])           # rank-local energies; the oracle reports the global sums
     assert max(abs(a - b) / abs(b) for a, b in zip(pe, pe_ref) if abs(b) > 1e-6) <= 1e-9
 
@@ -149,10 +115,6 @@ def test_native_rccl_transport_self_loop(qeq_mode, overlap, direct, monkeypatch)
     """The native transport (rccl_comm.hip: ncclSend/ncclRecv/ncclAllReduce on the engine's stream) on ONE GPU: a single rank is
     pushed through the staged six-stage exchange (RXMD_FORCE_STAGED) and every message through RCCL send/recv to itself
     (RXMD_FORCE_REMOTE) -- the code path of vprocs > 1 minus the wire.  Must reproduce the single-rank oracle trajectory."""
-    import sys, os
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    import oracle_api as oa
-    from test_gpu_parity import _engine, _oracle, q_err, f_err
     monkeypatch.setenv("RXMD_FORCE_STAGED", "1")
     monkeypatch.setenv("RXMD_FORCE_REMOTE", "1")
     if not overlap:          # default: the (hs,ht) halo runs on a second stream under the interior rows of the matrix pass (qeq_mode 1)
@@ -177,7 +139,6 @@ def test_native_rccl_transport_self_loop(qeq_mode, overlap, direct, monkeypatch)
 def test_pqeq_through_the_multi_rank_path_self_loop(monkeypatch):
     """PQEq on the vprocs > 1 code path (staged exchange + RCCL self send/recv): shell positions and charges travel as halos,
     the shell displacement migrates with its atom (14 doubles per record, comm.F90:153,165-167); against the clean oracle"""
-    from test_gpu_parity import _engine, _oracle, q_err, f_err
     monkeypatch.setenv("RXMD_FORCE_STAGED", "1")
     monkeypatch.setenv("RXMD_FORCE_REMOTE", "1")
     kw = dict(QEq_tol=1e-12, NMAXQEq=2000)
@@ -197,27 +158,15 @@ def test_pqeq_through_the_multi_rank_path_self_loop(monkeypatch):
 
 # ---- round 6: every MODE of the driver between DISTINCT ranks (until now only plain isQEq 1 had left a self loop) ---------------------------------
 def _run_ranks(spec, world, timeout=900):
-    ctx = mp.get_context("spawn")
-    with ctx.Manager() as m:
-        out = m.dict()
-        port = _port()
-        ps = [ctx.Process(target=mr_worker.engine_rank_mode, args=(r, world, port, spec, out)) for r in range(world)]
-        [p.start() for p in ps]; [p.join(timeout) for p in ps]
-        for p in ps:
-            if p.is_alive():
-                p.kill()
-        assert len(out) == world, "a rank died or hung"
-        res = [out[r] for r in range(world)]
+    res = run_ranks(mr_worker.engine_rank_mode, world, spec, timeout=timeout)
     for o in res:
-        assert "error" not in o, o.get("error")
         assert o["err"] == "None"
         assert o["nex"] > 0 and o["nar"] > 0 and o["nghost"] > 0
     return res
 
 
 def _rank_errs(q, f, qref, fref):
-    qrms = np.sqrt((qref ** 2).mean()); frms = np.sqrt((fref ** 2).mean())
-    return ((np.abs(q - qref) / np.maximum(np.abs(qref), qrms)).max(), (np.abs(f - fref).max(axis=1) / np.maximum(np.abs(fref).max(axis=1), frms)).max())
+    return q_err(q, qref), f_err(f, fref)
 
 
 @pytest.mark.parametrize("vp,direct", [((2, 1, 1), False), ((2, 1, 1), True), ((2, 2, 2), False), ((2, 2, 2), True)])

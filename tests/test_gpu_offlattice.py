@@ -59,7 +59,7 @@ import pytest
 
 import oracle_api as oa
 import offlattice_systems as ol
-from test_gpu_parity import q_err, f_err, e_err, compare_bond_order_taps, QTOL, FTOL, ETOL
+from parity import q_err, f_err, e_err, compare_bond_order_taps, rec10, QTOL, FTOL, ETOL
 
 pytestmark = pytest.mark.gpu
 
@@ -126,7 +126,7 @@ def _engine(name, with_v=False, lattice=None, **kw):
     import rxmd_amd
     ff, lat2, ranks, v = ol.build(name)
     e = rxmd_amd.RxmdEngine(ff, lat2 if lattice is None else lattice, **kw)
-    e.set_atoms_rxff(ol.rec10(ranks, v if with_v else None))
+    e.set_atoms_rxff(rec10(ranks[0], v if with_v else None))
     return e
 
 

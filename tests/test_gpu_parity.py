@@ -14,42 +14,9 @@ import numpy as np
 import pytest
 
 import oracle_api as oa
+from parity import _engine, _oracle, q_err, f_err, e_err, compare_bond_order_taps, _rec10_from_oracle, QTOL, FTOL, ETOL
 
 pytestmark = pytest.mark.gpu
-
-QTOL = 1e-6
-FTOL = 1e-6
-ETOL = 1e-9
-
-
-def _engine(case, mc, **kw):
-    import rxmd_amd
-    from rxmd_amd import system
-    ff, names, frac, lat = oa.make_system(case)
-    lat3, rec = system.geninit(ff, names, frac, lat, mc=mc, lg=kw.get("lg", False))
-    e = rxmd_amd.RxmdEngine(ff, lat3, **kw)
-    e.set_atoms_rxff(rec)
-    return e
-
-
-def _oracle(case, mc, **kw):
-    ff, names, frac, lat = oa.make_system(case)
-    lat2, ranks = oa.geninit(names, frac, lat, oa.ffield_names(ff, lg=kw.get("lg", False)), mc=mc)
-    return oa.Oracle(ff, lat2, ranks, **kw)
-
-
-def q_err(q, qref):
-    qrms = np.sqrt((qref ** 2).mean())
-    return (np.abs(q - qref) / np.maximum(np.abs(qref), max(qrms, 1e-300))).max()
-
-
-def f_err(f, fref):
-    frms = np.sqrt((fref ** 2).mean())
-    return (np.abs(f - fref).max(axis=1) / np.maximum(np.abs(fref).max(axis=1), frms)).max()
-
-
-def e_err(pe, pref):
-    return max(abs(a - b) / abs(b) for a, b in zip(pe, pref) if abs(b) > 1e-6)
 
 
 def test_library_is_the_hip_build():
@@ -93,38 +60,6 @@ def check_bond_order_taps(e, o):
     compare_bond_order_taps(dict(deltap=e.debug(1), delta=e.debug(0), cd=e.debug(8), cc=e.debug(10), cnt=cnt, pg=pg, bo=bo),
                             dict(deltap=o.get(102), delta=o.get(101), cd=o.get(110), cc=o.get(109), cnt=o.get(103)[:n], nbr=onbr[:n], bo=obo[:n], gidG=gidG,
                                  pos=o.get(100, width=3)), n, np.asarray(e.lattice[:3]))
-
-
-def compare_bond_order_taps(E, O, n, box, rtol=1e-10):
-    """E: the engine's taps, O: the oracle's.  Tolerance 1e-10, not 1e-12: the reference sends ALL positions through normalised coordinates and
-    back in every COPYATOMS call (comm.F90:222-227,260-264; two calls per CG iteration), which moves them by ~1e-12 A before FORCE sees
-    them; the engine keeps the residents where they are.  1e-12 A x d(BO')/dr of a few per A = the 1e-11 measured on delta'."""
-    gidG = O["gidG"]
-    for k in ("deltap", "delta", "cd"):
-        assert np.abs(E[k] - O[k]).max() <= rtol * max(np.abs(O[k]).max(), 1.0), k
-    cnt = E["cnt"]
-    assert np.array_equal(cnt, O["cnt"].astype(cnt.dtype))
-    for i in range(n):
-        c = int(cnt[i])
-        ge, go = E["pg"][i, :c], gidG[O["nbr"][i, :c] - 1]
-        ie, io = np.lexsort((E["bo"][i, :c], ge)), np.lexsort((O["bo"][i, :c], go))      # an atom can be bonded to two images of one partner in a one-cell box
-        assert np.array_equal(ge[ie], go[io])
-        assert np.abs(E["bo"][i, :c][ie] - O["bo"][i, :c][io]).max(initial=0.0) <= rtol
-    # ccbnd.  The reference evaluates a torsion i-j-k-l once, from the centre atom with the smaller gid, and scatters the coefficient of the
-    # far bond k-l to WHICHEVER IMAGES of k and l that centre atom sees (pot.F90:1188-1215 -> ForceB); the engine books the far bond from k's
-    # own visit of the torsion, i.e. on the image of k that is a centre atom there (DESIGN.md 4).  Forces are linear in ccbnd and
-    # translation invariant, so after the CPBK fold both give the same forces, but per INDEX the two differ for atoms whose torsions cross
-    # the box.  What must agree: ccbnd summed over the images of an atom, and ccbnd per index for atoms deeper inside the box than any
-    # torsion reaches (3 bonds < 12 A) -- none in the boxes of 1-2 cut-offs, most of a 36k-atom box.
-    G = len(gidG)
-    scale = max(np.abs(O["cc"]).max(), 1.0)
-    se = np.bincount(gidG, weights=E["cc"][:G]); so = np.bincount(gidG, weights=O["cc"][:G])
-    assert np.abs(se - so).max() <= 1e-9 * scale
-    depth = np.minimum(O["pos"][:n], box - O["pos"][:n]).min(axis=1)
-    deep = depth > 12.0
-    if deep.any():
-        assert np.abs(E["cc"][:n][deep] - O["cc"][:n][deep]).max() <= 1e-9 * scale
-    return int(deep.sum())
 
 
 @pytest.mark.parametrize("case,npz", [("rdx168", "rdx168_tight"), ("rdx222", "rdx222_tight"), ("ice644", "ice644_tight")])
@@ -271,15 +206,6 @@ def test_iteration_statistics_over_1000_steps(qeq_mode, win, monkeypatch):
     assert dqs.max() <= 5.0 * ref_dq.max()       # (the single worst of 1,000 calls is the noisiest of these numbers -- an early chance exit in the middle of a solve; the hydrogen-bond atomics make the
                                                  #  trajectory, hence the draw, differ from run to run: measured 0.8-1.6 x over eleven runs, the gate leaves room for the tail)
     e.close(); t.close()
-
-
-def _rec10_from_oracle(o, lat):
-    """rxff.bin records of the oracle's present state (orthorhombic box, one rank)"""
-    n = len(o.gids())
-    rec = np.zeros((n, 10))
-    rec[:, 0:3] = o.pos() / np.asarray(lat[:3]); rec[:, 3:6] = o.vel(); rec[:, 6] = o.charges()
-    rec[:, 7] = o.types() + o.gids() * 1e-13
-    return rec
 
 
 @pytest.mark.parametrize("qeq_mode", [0, 1])

@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 import oracle_api as oa
-from test_gpu_parity import QTOL, FTOL, ETOL, q_err, f_err, e_err, _engine, _oracle
+from parity import QTOL, FTOL, ETOL, q_err, f_err, e_err, _engine, _oracle
 
 pytestmark = pytest.mark.gpu
 

@@ -24,40 +24,13 @@ import numpy as np
 import pytest
 
 import oracle_api as oa
-from test_gpu_parity import q_err, f_err, e_err, compare_bond_order_taps, QTOL, FTOL, ETOL
+import mr_worker
+from ranks import run_ranks
+from parity import _engine, _oracle, q_err, f_err, e_err, compare_bond_order_taps, rec10, _perturbed_rdx, KW, QTOL, FTOL, ETOL
 
 pytestmark = pytest.mark.gpu
 
-MC = (6, 6, 6)
-KW = dict(QEq_tol=1e-300, NMAXQEq=100)
 NSTEPS = 3
-
-
-def _perturbed_rdx(vprocs=(1, 1, 1)):
-    """RDX 6x6x6 as geninit lays it out, every atom displaced by N(0, 0.05 A) per component, velocities N(0, 0.05) (230 K); with vprocs the
-    atoms are dealt to the domains of the rank grid the way geninit does (geninit.F90:493-527) -> (ffield, lattice, per-rank dicts, per-rank v)"""
-    ff, names, frac, lat = oa.make_system("rdx168")
-    lat2, ranks = oa.geninit(names, frac, lat, oa.ffield_names(ff), mc=MC)
-    rng = np.random.default_rng(2026)
-    n = len(ranks[0]["type"])
-    rn = ranks[0]["rnorm"] + rng.normal(0, 0.05, (n, 3)) / np.asarray(lat2[:3])
-    # back into [0, 1) like geninit (geninit.F90:476-480) and every COPYATOMS(MODE_MOVE) leave them: a resident outside the box is not
-    # a state the reference's driver produces (its QEq ghost shell of exactly rctap would miss partners of such an atom)
-    rn = rn - np.floor(rn)
-    v = rng.normal(0, 0.05, (n, 3))
-    if tuple(vprocs) == (1, 1, 1):
-        ranks[0]["rnorm"] = rn
-        return ff, lat2, ranks, v
-    vp = np.array(vprocs)
-    dom = (rn * vp).astype(np.int64)
-    sid = dom[:, 0] + dom[:, 1] * vp[0] + dom[:, 2] * vp[0] * vp[1]
-    out, vs = [], []
-    for p in range(int(vp.prod())):
-        sel = np.nonzero(sid == p)[0]
-        obox = (1.0 / vp) * np.array([p % vp[0], (p // vp[0]) % vp[1], p // (vp[0] * vp[1])])
-        out.append(dict(rnorm=rn[sel] - obox, type=ranks[0]["type"][sel].copy(), gid=ranks[0]["gid"][sel].copy()))
-        vs.append(v[sel].copy())
-    return ff, lat2, out, vs
 
 
 @pytest.fixture(scope="module")
@@ -80,12 +53,8 @@ def oracle36k():
 def _engine36k(qeq_mode):
     import rxmd_amd
     ff, lat2, ranks, v = _perturbed_rdx()
-    r = ranks[0]
-    n = len(r["type"])
-    rec = np.zeros((n, 10))
-    rec[:, 0:3] = r["rnorm"]; rec[:, 3:6] = v; rec[:, 7] = r["type"] + r["gid"] * 1e-13
     e = rxmd_amd.RxmdEngine(ff, lat2, qeq_mode=qeq_mode, **KW)
-    e.set_atoms_rxff(rec)
+    e.set_atoms_rxff(rec10(ranks[0], v))
     return e
 
 
@@ -169,7 +138,6 @@ def test_forces_of_the_979776_atom_crystal_by_periodicity():
     """BASELINE configs[1] at full size: per-atom forces and charges of all 16^3 interior unit cells of RDX 18 x 18 x 18 against an interior
     cell of a 4 x 4 x 4 ORACLE run.  An interior cell has every bonded partner among the residents, in the same relative index order
     (cells are numbered x-major in both systems), so the `nbr < i` rule of ForceBondedTerms selects the same terms."""
-    from test_gpu_parity import _engine, _oracle
     kw = dict(QEq_tol=1e-12, NMAXQEq=2000)
     o = _oracle("rdx168", (4, 4, 4), **kw); o.qeq(); o.force()
     qo = o.charges().reshape(4, 4, 4, 168); fo = o.forces().reshape(4, 4, 4, 168, 3)
@@ -202,9 +170,6 @@ def test_perturbed_rdx_36k_on_several_ranks_against_the_multi_rank_oracle(vp, di
     domain has interior rows (the two-launch matrix pass under the halo) and boundary rows; on 2 x 2 x 2 (domains of 39 x 35 x 32 A) ghosts
     reach a rank through the edge / corner forwarding of comm.F90:68-86 (x, then y carrying x's ghosts, then z carrying both) while interior
     groups run under the halo.  `direct`: the owner-to-ghost vector halo (7 peers per rank on 2 x 2 x 2)."""
-    import socket
-    import torch.multiprocessing as mp
-    import mr_worker
     world = vp[0] * vp[1] * vp[2]
     if direct:
         monkeypatch.setenv("RXMD_HALO_DIRECT", "1")
@@ -214,20 +179,9 @@ def test_perturbed_rdx_36k_on_several_ranks_against_the_multi_rank_oracle(vp, di
     nmax = max(len(r["type"]) for r in ranks)
     o = oa.Oracle(ff, lat2, ranks, vprocs=vp, nbuffer=(10 if world == 2 else 12) * nmax, v0=vs, **KW)
     o.qeq(); o.force(); o.step(NSTEPS)
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    ctx = mp.get_context("spawn")
-    with ctx.Manager() as m:
-        out = m.dict()
-        ps = [ctx.Process(target=mr_worker.engine_rank_perturbed, args=(r, world, port, vp, NSTEPS, 1, out)) for r in range(world)]
-        [p.start() for p in ps]; [p.join(1200) for p in ps]
-        for p in ps:
-            if p.is_alive():
-                p.kill()
-        assert len(out) == world, "a rank died or hung"
-        res = [out[r] for r in range(world)]
+    res = run_ranks(mr_worker.engine_rank_perturbed, world, vp, NSTEPS, 1, timeout=1200)
     moved = 0
     for r, x in enumerate(res):
-        assert "error" not in x, x.get("error")
         assert x["err"] == "None"
         assert 0 < x["n_boundary_rows"] < x["natoms"]
         assert np.array_equal(x["gid"], o.gids(r))
@@ -247,7 +201,6 @@ def test_forces_of_the_full_size_water_and_sicnp_crystals_by_periodicity(case, m
     gid-ordered torsion booking select the same terms; energies cannot see that rule, forces do).  With the engine's own charges the forces follow the
     charges' CG truncation; with the oracle's charges injected (those of EVERY cell by periodicity; PQEq: shells on their cores at step 0,
     pqeq.F90:361-435) the parity tolerance 1e-6."""
-    from test_gpu_parity import _engine, _oracle
     kw = dict(QEq_tol=1e-12, NMAXQEq=2000)
     if case == "sicnp":
         kw["pqeq"] = oa.PQEQ_SICNP

@@ -14,58 +14,11 @@ import numpy as np
 import pytest
 
 import oracle_api as oa
-from test_gpu_parity import q_err, f_err, QTOL, FTOL
+from parity import q_err, f_err, perturbed_rdx, run, lattice_sequence, QTOL, FTOL, SWITCH, CLEAN
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SWITCH = "RXMD_STREAMS_BY_PLACE"
-KW = dict(QEq_tol=1e-7, NMAXQEq=500, qeq_mode=1)      # (qeq_mode 1: the run-ahead CG loop in row order, the path of the benchmark)
-CLEAN = (SWITCH, "RXMD_FORCE_STAGED", "RXMD_FORCE_REMOTE", "RXMD_NB10_ALWAYS", "RXMD_SPMV_WIN", "RXMD_NONBOND_WIN", "RXMD_QEQ_F32")
-
-
-def perturbed_rdx(mc, scale=1.0, sigma=0.05):
-    """the recipe of test_gpu_scale.py: RDX as geninit lays it out, every atom displaced by N(0, sigma A) per component (default_rng(2026)), wrapped
-    into [0, 1), velocities N(0, 0.05); scale multiplies the three edges (the normalised coordinates stay) -> (ffield, lattice, rec10)"""
-    ff, names, frac, lat = oa.make_system("rdx168")
-    lat2, ranks = oa.geninit(names, frac, lat, oa.ffield_names(ff), mc=mc)
-    lat2 = [lat2[0] * scale, lat2[1] * scale, lat2[2] * scale] + list(lat2[3:6])
-    rng = np.random.default_rng(2026)
-    r = ranks[0]
-    n = len(r["type"])
-    rn = r["rnorm"] + rng.normal(0, sigma, (n, 3)) / np.asarray(lat2[:3])
-    rn = rn - np.floor(rn)
-    rec = np.zeros((n, 10))
-    rec[:, 0:3] = rn; rec[:, 3:6] = rng.normal(0, 0.05, (n, 3)); rec[:, 7] = r["type"] + r["gid"] * 1e-13
-    return ff, lat2, rec
-
-
-def run(ff, lat, rec, place, monkeypatch, nsteps=3, env=(), bits=None, rccl=False, before=None, **kw):
-    """QEq(); FORCE(); step(nsteps) on a fresh engine with the switch set -> what the layouts are compared on, behind FORCE (0) and behind the steps"""
-    import rxmd_amd
-    for k in CLEAN:
-        monkeypatch.delenv(k, raising=False)
-    monkeypatch.setenv(SWITCH, str(place))
-    for k, v in env:
-        monkeypatch.setenv(k, v)
-    e = rxmd_amd.RxmdEngine(ff, lat, **dict(KW, **kw))
-    if rccl:
-        e.init_rccl(e.rccl_unique_id(), 0, 1)
-    e.set_atoms_rxff(rec)
-    if bits:
-        e.set_qeq_precision(bits)
-    out = {}
-    if before:
-        before(e, out)
-    it0, _ = e.QEq(); e.FORCE(); a = e.atoms(); st = e.stats()
-    out.update(it0=it0, est0=e.debug(13).copy(), q0=a["q"].copy(), f0=a["f"].copy(), rows0=e.debug(7).copy(), layout0=st["streams_by_place"], stats0=st,
-               tap14=e.debug(14, cap=2).copy())      # (1 if the poison pattern is on, an element of the value stream that no kernel writes)
-    e.step(nsteps)
-    a = e.atoms(); st = e.stats()
-    out.update(est=e.debug(13).copy(), q=a["q"].copy(), f=a["f"].copy(), pos=a["pos"].copy(), gid=a["gid"].copy(), rows=e.debug(7).copy(), iters=st["qeq_iters_total"],
-               layout=st["streams_by_place"], stats=st, stride=st["n10_stride"])
-    e.close()
-    return out
 
 
 def same_bits(a, b, keys=("it0", "est0", "q0", "rows0", "est", "q", "pos", "gid", "rows", "iters")):
@@ -189,12 +142,11 @@ def test_row_stride_growth_keeps_layout_and_results(monkeypatch):
 
 
 def test_set_lattice_growth_of_the_window_groups_keeps_layout_and_results(monkeypatch):
-    """RDX 2 x 2 x 2, then set_lattice to the expanded cell of test_gpu_variable_cell_oracle.lattice_sequence (more cells on every axis: the
+    """RDX 2 x 2 x 2, then set_lattice to the expanded cell of parity.lattice_sequence (more cells on every axis: the
     window-group arrays are allocated again), then 2 steps.  Both layouts through the same call sequence: the same bits, the flag as set.  Against a
     fresh engine that starts in the expanded cell with the same normalised coordinates, both with converged charges (QEq_tol 1e-12): the parity
     tolerances of the suite (its positions are rnorm x lattice, the live engine's an affine map of its old ones: an ulp apart, which the REAL(4)
     rounding of r^2 in the matrix turns into 6e-8 of an entry where it flips)."""
-    from test_gpu_variable_cell_oracle import lattice_sequence
     ff, lat, rec = perturbed_rdx((2, 2, 2))
     seq = {}
 

@@ -13,33 +13,23 @@ rdx-dilute (167 angles in the 2 A shell, most triples empty, one atom without a 
 kernels take another path: every row type in one walk of the LDS histogram, several walks, and no LDS at all (structure.hip: SP_HCAP, SA_HCAP)."""
 import ctypes as C
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
 
 import oracle_api as oa
 import offlattice_systems as ol
 import structure_reference as sr
 import structure_worker
-import graph_worker
+from ranks import run_ranks
 from npt_reference import hmat
-from test_gpu_parity import _engine
-from test_gpu_pair_graph import _make, rebuild, brute_force
+from parity import _engine, build_system, rec10, code as _code
+from graph_support import _make, rebuild, brute_force, KW5
 
 pytestmark = pytest.mark.gpu
 
-KW5 = dict(QEq_tol=1e-300, NMAXQEq=5)
 _BF = {}
-
-
-def _code(call):
-    import rxmd_amd
-    with pytest.raises(rxmd_amd.RxmdError) as ei:
-        call()
-    return ei.value.code
 
 
 def _nso(e):
@@ -239,26 +229,13 @@ def test_variable_cell_books_the_new_volume_and_keeps_the_accumulators():
 
 
 # ---- 3. ranks ------------------------------------------------------------------------------------------------------------------------------------
-def _port():
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
 
 
 def test_rank_summed_counts_equal_the_single_rank_counts(tmp_path):
     from rxmd_amd import structure
     base = dict(case="rdx222", mc=(2, 2, 2), shaken=(2048, 0.05), kw=KW5, begin=(sr.R_MAX, sr.NBINS_R, sr.SHELLS, sr.NBINS_A), dir=str(tmp_path))
     spec = dict(base, vp=(2, 1, 1))
-    ctx = mp.get_context("spawn")
-    with ctx.Manager() as m:
-        out = m.dict()
-        port = _port()
-        ps = [ctx.Process(target=structure_worker.structure_rank, args=(r, 2, port, spec, out)) for r in range(2)]
-        [p.start() for p in ps]; [p.join(600) for p in ps]
-        for p in ps:
-            if p.is_alive():
-                p.kill()
-        assert len(out) == 2, "a rank died or hung"
-        for r in range(2):
-            assert "error" not in out[r], out[r].get("error")
+    run_ranks(structure_worker.structure_rank, 2, spec, timeout=600)
     dicts = []
     for r in range(2):
         with np.load(os.path.join(str(tmp_path), "rank%d.npz" % r)) as f:
@@ -269,9 +246,9 @@ def test_rank_summed_counts_equal_the_single_rank_counts(tmp_path):
     assert all(d["natoms"] > 0 for d in dicts) and sum(d["natoms"] for d in dicts) == 1344
     whole = structure.merge(dicts)
     import rxmd_amd
-    ff, lat, ranks, vs = graph_worker.build_system(dict(base, vp=(1, 1, 1)))
+    ff, lat, ranks, vs = build_system(dict(base, vp=(1, 1, 1)))
     e = rxmd_amd.RxmdEngine(ff, lat, **KW5)
-    e.set_atoms_rxff(graph_worker.rec10(ranks[0])); e.QEq(); e.FORCE()
+    e.set_atoms_rxff(rec10(ranks[0])); e.QEq(); e.FORCE()
     one = _sample_once(e, sr.R_MAX, sr.NBINS_R, sr.SHELLS, sr.NBINS_A)
     for k in ("pair_counts", "angle_counts", "atoms_per_type"):
         assert np.array_equal(whole[k], one[k]), k

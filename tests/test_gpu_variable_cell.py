@@ -4,14 +4,15 @@ A new lattice keeps every resident's normalised coordinates (r' = H' H^-1 r on t
 so QEq + FORCE after set_lattice(L1) must be what a fresh engine built at L1 from the same fractional input computes, and what the oracle
 computes there.  The barostat couples on the step's own stress sums (the astr that PRINTE prints) and scales the lattice lengths."""
 import os
-import socket
 import numpy as np
 import pytest
 
 import oracle_api as oa
 import npt_reference as npt
 from npt_reference import mu_np as _mu_np, volume as _volume, hmat as _hmat
-from test_gpu_parity import _engine, _oracle, q_err, f_err, e_err, QTOL, FTOL, ETOL
+from ranks import run_ranks
+import vc_worker
+from parity import _engine, _oracle, q_err, f_err, e_err, QTOL, FTOL, ETOL
 
 pytestmark = pytest.mark.gpu
 
@@ -334,27 +335,12 @@ def test_pqeq_shells_follow_the_lattice():
     e.close(); f.close()
 
 
-def _port():
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
-
-
 def test_two_ranks_couple_to_the_same_lattice():
     """vprocs (2,1,1), two processes on one GPU over gloo.  The virial of the first FORCE summed over the two ranks is the one-rank virial and
     the oracle's two-rank sum; 10 isotropic couplings give the same lattice on both ranks bit for bit, and every one of them and the final
     energies are those of the two-rank oracle under the numpy barostat (tests/npt_reference.py) started from the engine's velocities; a rank
     given another lattice makes set_lattice fail with RXMD_E_ARG on both"""
-    import torch.multiprocessing as mp
-    import vc_worker
-    ctx = mp.get_context("spawn")
-    with ctx.Manager() as m:
-        out = m.dict()
-        port = _port()
-        ps = [ctx.Process(target=vc_worker.barostat_rank, args=(r, 2, port, 10, out)) for r in range(2)]
-        [p.start() for p in ps]; [p.join(600) for p in ps]
-        assert len(out) == 2, "a rank died"
-        res = [out[r] for r in range(2)]
-    for o in res:
-        assert "error" not in o, o.get("error")
+    res = run_ranks(vc_worker.barostat_rank, 2, 10, timeout=600)
     one = vc_worker.barostat_run((1, 1, 1), 0, 10)
     ff, names, frac, lat = oa.make_system("rdx222")
     lat2, ranks = oa.geninit(names, frac, lat, oa.ffield_names(ff), mc=(2, 2, 2), vprocs=(2, 1, 1))

@@ -14,13 +14,14 @@ Gates (none is new): static evaluations QTOL / FTOL / ETOL of test_gpu_parity an
 component; where the clamp binds mu is 1 +- max_strain exactly on both sides and the lattices agree to 1e-14 per coupling.
 Velocities are one seeded numpy draw given to both programs.  Run with -s for the measured margins."""
 import functools
-import socket
 import numpy as np
 import pytest
 
 import oracle_api as oa
 import npt_reference as npt
-from test_gpu_parity import _engine, q_err, f_err, e_err, QTOL, FTOL, ETOL
+from ranks import run_ranks
+import vc_worker
+from parity import _engine, q_err, f_err, e_err, sheared, lattice_sequence, QTOL, FTOL, ETOL
 
 pytestmark = pytest.mark.gpu
 
@@ -52,11 +53,6 @@ def engine_for(case, v=None, **kw):
     if v is not None:
         e.set_velocities(v)                              # one rank: the local order of the records is the gid order
     return e
-
-
-def sheared(L0):
-    """lengths times (1.03, 0.98, 1.01), alpha - 3, beta + 2, gamma - 2.5 degrees"""
-    return [L0[0] * 1.03, L0[1] * 0.98, L0[2] * 1.01, L0[3] - 3.0, L0[4] + 2.0, L0[5] - 2.5]
 
 
 def assert_sheared(L0, L1):
@@ -142,13 +138,6 @@ def test_pqeq_calls_repeated_without_moving_the_atoms():
         print("   shells %.2e A (gate 1e-07), largest displacement %.2e A" % (ds, np.abs(o.spos()).max()))
         assert ds <= 1e-7
     e.close()
-
-
-def lattice_sequence(L0, maxrc):
-    """3: expansion that adds 10 A grid cells on every axis, shear, z compressed below a bond-cell threshold, back"""
-    cz = int(L0[2] / maxrc)
-    return [("expanded", [L0[0] * 1.05, L0[1] * 1.05, L0[2] * 1.10] + L0[3:]), ("sheared", sheared(L0)),
-            ("compressed", L0[:2] + [cz * maxrc - 0.05] + L0[3:]), ("back at L0", list(L0))]
 
 
 def test_a_sequence_of_lattices_on_one_engine():
@@ -389,27 +378,11 @@ def test_a_coupling_lowers_a_cell_count_inside_step():
 
 
 # ------------------------------------------------------------------------------------------------ 10, 11: two ranks over gloo
-def _port():
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
 
 
 def two_ranks(job):
-    """two spawned children on one GPU, each joined with a time limit; a dead rank fails the test, nothing is retried"""
-    import torch.multiprocessing as mp
-    import vc_worker
-    ctx = mp.get_context("spawn")
-    with ctx.Manager() as m:
-        out = m.dict()
-        port = _port()
-        ps = [ctx.Process(target=vc_worker.npt_rank, args=(r, 2, port, job, out)) for r in range(2)]
-        [p.start() for p in ps]; [p.join(600) for p in ps]
-        alive = [p for p in ps if p.is_alive()]
-        [p.kill() for p in alive]
-        assert not alive and len(out) == 2, "a rank died or did not finish"
-        res = [out[r] for r in range(2)]
-    for r in res:
-        assert "error" not in r, r.get("error")
-    return res
+    """two spawned children on one GPU under one time limit; a dead rank fails the test, nothing is retried"""
+    return run_ranks(vc_worker.npt_rank, 2, job, timeout=600)
 
 
 def gate_two_ranks(tag, res, o, rows, clamped, hot):

@@ -11,23 +11,10 @@ import pytest
 
 import oracle_api as oa
 import npt_reference as npt
+from parity import q_err, f_err, e_err
 
 TIGHT = dict(QEq_tol=1e-12, NMAXQEq=2000)
 SYSTEMS = {"rdx222": (2, 2, 2), "ice644": (6, 4, 4), "mos2_tri324": (3, 3, 2), "sicnp547": (1, 1, 1)}
-
-
-def q_err(q, qref):
-    qrms = np.sqrt((qref ** 2).mean())
-    return (np.abs(q - qref) / np.maximum(np.abs(qref), max(qrms, 1e-300))).max()
-
-
-def f_err(f, fref):
-    frms = np.sqrt((fref ** 2).mean())
-    return (np.abs(f - fref).max(axis=1) / np.maximum(np.abs(fref).max(axis=1), frms)).max()
-
-
-def e_err(pe, pref):
-    return max(abs(a - b) / abs(b) for a, b in zip(pe, pref) if abs(b) > 1e-6)
 
 
 def build(case, lat=None, vp=(1, 1, 1), ranks=None, **kw):

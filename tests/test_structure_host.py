@@ -129,7 +129,7 @@ def test_angle_distribution_and_merge():
 @pytest.mark.parametrize("case", ["rdx-shaken", "rdx-denser", "rdx-dilute"])
 def test_near_edge_share_of_the_brute_force_on_disordered_boxes(case):
     import structure_reference as sr
-    from test_gpu_pair_graph import brute_force
+    from graph_support import brute_force
     pos, type0, lat, nso = sr.host_positions(case)
     bf = brute_force(pos, lat, sr.R_MAX)
     p = sr.bin_pairs(bf, type0, nso, sr.R_MAX, sr.NBINS_R)
