@@ -1,4 +1,4 @@
-// assemble.hip -- turns the per-slot accumulators of bonded.hip into forces, and the MD step.
+// assemble.hip -- turns the per-slot accumulators of the bonded terms (bonded.hip, angles.hip, torsions.hip, hbonds.hip) into forces, and the MD step.
 //   ForceBondedTerms + ForceD   reference src/pot.F90:113-144, 1230-1273  -> k_cd_gather, k_ccbnd_terms / _sum, k_bond_force_terms / _sum
 //   COPYATOMS(MODE_CPBK)        reference src/comm.F90:385-396, 474-482   -> Engine::fold_ghost_forces (exchange.hip)
 //   FORCE driver                reference src/pot.F90:2-90                -> Engine::force

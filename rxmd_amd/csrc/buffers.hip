@@ -134,7 +134,7 @@ void Engine::declare_buffers() {
   for (double **t : {&bo0, &bo1, &bo2, &bo3, &dln2, &dln3, &dBOp, &A0, &A1, &A2, &A3, &cf1, &cf2, &cf3, &cdn, &fnx, &fny, &fnz, &etor, &econ, &epen, &ecoa, &bt1, &bt2, &bt3})
     b.add(*t, G_BOND, Dim::Cap, 1, 0, P, whole);
   b.add(ehb_don, G_SETUP, Dim::Rows10, 1, EHB_DON_EXTRA, P, whole);
-  b.add(ehb_cnt, G_SETUP, Dim::Fixed, 0, 72, Z, never);      // 64 sub-lists (bonded.hip EHB_REGIONS) + debug words
+  b.add(ehb_cnt, G_SETUP, Dim::Fixed, 0, 72, Z, never);      // 64 sub-lists (hbonds.hip EHB_REGIONS) + debug words
   b.add(ecoef, G_SETUP, Dim::NB, 6, 0, P, whole);
   b.add(deltap, G_SETUP, Dim::NB, 1, 0, P, whole);
   b.add(delta, G_SETUP, Dim::NB, 1, 0, P, whole);

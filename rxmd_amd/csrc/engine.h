@@ -182,6 +182,26 @@ __device__ inline double wave_sum64(double v) {
   v += dpp_move<0x143, 0xc>(v);    // row_bcast:31 into rows 2 and 3: lane 63 holds the total
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
 }
+// LDS hand-off between the lanes of ONE wavefront: what its lanes stored to LDS is visible to its other lanes behind this.  (The LDS queue of a wave
+// is in order; the fences only stop the compiler from moving accesses across.)
+__device__ inline void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Timing probes of the experiments build (`make experiments`, -DRXMD_EXPERIMENTS) inside kernels of the step's path: "is probe n set" / "is one of
+// these probe bits set" -- the literal false in the product build, so a statement guarded by one is written once and the product build's compiler
+// drops it before it generates code (macros, not functions: a function's argument, the probe word, is no constant expression, and the guarded
+// branch would reach the optimiser).  exp_probe is spelt !(word != n): most uses are negated, and `!exp_probe(w, n)` then reaches the compiler as the
+// `w != n` it replaced -- with (word == n) the one-visit torsion kernels of the experiments build come out with other registers.
+#ifdef RXMD_EXPERIMENTS
+#define exp_probe(word, n) (!((word) != (n)))
+#define exp_probe_mask(word, bits) (((word) & (bits)) != 0)
+#else
+#define exp_probe(word, n) false
+#define exp_probe_mask(word, bits) false
+#endif
 
 #ifndef WIN_ROWS_DEF
 #define WIN_ROWS_DEF 16
@@ -235,7 +255,7 @@ struct Buffers {
   std::vector<std::vector<char>> save_residents(const Engine &e) const;
   void restore_residents(const std::vector<std::vector<char>> &h);
 };
-constexpr size_t EHB_DON_EXTRA = 64 * 256 + 256;   // donor list beyond one entry per row: 64 sub-lists (bonded.hip EHB_REGIONS) padded to 256
+constexpr size_t EHB_DON_EXTRA = 64 * 256 + 256;   // donor list beyond one entry per row: 64 sub-lists (hbonds.hip EHB_REGIONS) padded to 256
 
 // engine state that a block changes and every way out of it, an exception included, puts back
 template <class T> struct Restore {                   // a value: what `ref` held when the block was entered
@@ -321,12 +341,12 @@ struct Engine {
   double *etor = nullptr, *econ = nullptr, *epen = nullptr, *ecoa = nullptr;   // per-bond exponentials shared by many angles/torsions
   double *bt1 = nullptr, *bt2 = nullptr, *bt3 = nullptr;                        // per-bond scratch: terms a lane-per-bond kernel leaves for the per-atom sum behind it
   double *ecoef = nullptr;                                                      // 6 per-atom coefficients of Elnpr (bonded.hip)
-  // one-visit torsions (bonded.hip, k_e4b<*, true>): the k-l side of a torsion -- ForceB coefficient of bond k-l and the force on l, summed over i -- per
+  // one-visit torsions (torsions.hip, k_e4b<*, true>): the k-l side of a torsion -- ForceB coefficient of bond k-l and the force on l, summed over i -- per
   // (bond (k, l1), slot of j in the list of k), TW columns per bond, with one flag byte per entry (all zero between FORCE calls)
   double4 *e4b_t = nullptr; unsigned char *e4b_flag = nullptr; size_t e4b_cap = 0; bool e4b_dirty = false;
   void alloc_e4b_delivery(size_t entries);
   int nbonds_res = 0;                                                           // bonds of the residents = boff[N]: the first nbonds_res entries of the tables
-  int2 *ehb_don = nullptr; size_t ehb_don_cap = 0; int *ehb_cnt = nullptr; unsigned ehb_donor_types = 0u; int ehb_blocks_per_cu = 0, ehb_blocks_per_cu_sl = 0; // (_sl: of the sweep over the window slots) hydrogen bonds (bonded.hip): donor list (atom, mask of its hydrogen slots), its length, types X with a row (X, H = 2, any)
+  int2 *ehb_don = nullptr; size_t ehb_don_cap = 0; int *ehb_cnt = nullptr; unsigned ehb_donor_types = 0u; int ehb_blocks_per_cu = 0, ehb_blocks_per_cu_sl = 0; // (_sl: of the sweep over the window slots) hydrogen bonds (hbonds.hip): donor list (atom, mask of its hydrogen slots), its length, types X with a row (X, H = 2, any)
   double *deltap = nullptr, *delta = nullptr, *nlp = nullptr, *dDlp = nullptr, *deltalp = nullptr;
   double *cds = nullptr, *cd = nullptr, *cc_ = nullptr;
   // 10 A list
@@ -344,6 +364,7 @@ struct Engine {
   double *scal = nullptr;      // device scalars (CG state)
   double *h_scal = nullptr;    // pinned host mirror
   int *d_err = nullptr, *h_err = nullptr, *h_cnt = nullptr;   // h_err: pinned, H_ERR_INTS ints: H_ERR_WORDS of the device error words, then h_cnt, the counts the host waits for (H_CNT_*)
+  int longest_bond_list() const { return h_err[2]; }          // of the step's list build (read back with the error word); 0 when no list is longer than 8
   double *xbuf_send = nullptr, *xbuf_recv = nullptr; size_t xbuf_doubles = 0; bool xbuf_owned = false;   // staged-exchange message buffers
   double pe[14] = {0}, astr[6] = {0};
 
@@ -610,7 +631,10 @@ struct Engine {
   void sorted_copy(const double2 *v);               // QCOPY1/QCOPY2 fused with the cell-sorted gather copy -> xs
   void fold_ghost_forces(double *fx, double *fy, double *fz);   // CPBK of a per-atom vector given by component (FORCE: frc)
   void bond_orders();
-  void bonded_energies();
+  void bonded_energies();                           // Ebond + Elnpr, then the three below (bonded.hip)
+  void valence_angles();                            // angles.hip
+  void torsions();                                  // torsions.hip
+  void hydrogen_bonds();                            // hbonds.hip
   void charge_halo();
   void nonbonded(bool to_fnb = false, bool energy = true);
   void pqeq_sorted_shells();      // ghost shells <- owners, cell-sorted copy (MODE_COPY payload of spos, comm.F90:129-131)

@@ -323,9 +323,7 @@ __global__ void __launch_bounds__(64 * L10_ROWS) k_list10(int N, int S10, Grid g
   // Phase 2, dense: one queued candidate per lane -> table interpolation, list entry, hessian value.  Only a third of the
   // candidates pass the distance test, so doing this work on compacted batches keeps every lane busy.
   auto emit = [&](int nproc) {
-#ifdef RXMD_EXPERIMENTS
-    if (g.probe == 2) { cnt += nproc; return; }
-#endif
+    if (exp_probe(g.probe, 2)) { cnt += nproc; return; }
     if (lane < nproc) {
       const int qw = sq[lane], slot = cnt + lane;
       if (slot < S10) {
@@ -380,9 +378,7 @@ __global__ void __launch_bounds__(64 * L10_ROWS) k_list10(int N, int S10, Grid g
           if (F32) h = static_cast<double>(static_cast<float>(h));     // the one rounding of the fp32 matrix stream
         }
         {   // window slot: the candidate's column (of this row) -> the group's table entry -> first unit of the column + offset inside it
-#ifdef RXMD_EXPERIMENTS
-          if (!(g.probe & 4))
-#endif
+          if (!exp_probe_mask(g.probe, 4))
           __builtin_nontemporal_store(static_cast<unsigned short>((k - cE[t_]) | (j >= N ? 0x8000 : 0)), sl10 + row + slot);     // cE: first position of the column's interval - 8 x its first unit
         }
         if (xs0) {
@@ -391,17 +387,13 @@ __global__ void __launch_bounds__(64 * L10_ROWS) k_list10(int N, int S10, Grid g
           if (PQ) rg += hc * qsj; else if (j >= N) rg += h * qsj;
         }
         anyghost |= (j >= N);
-#ifdef RXMD_EXPERIMENTS
-        if (!(g.probe & 8))
-#endif
+        if (!exp_probe_mask(g.probe, 8))
         if (nb10) {                                                     // (wave-uniform; nullptr: no kernel of this build reads the 4-byte entries, Engine::needs_nb10)
           unsigned ent = static_cast<unsigned>(k) | (static_cast<unsigned>(tj) << NB10_IDX_BITS) | (j >= N ? NB10_GHOST : 0u);
           if (SELFCHECK && gid[j] == gid[i]) ent |= NB10_SELF;         // an atom and its own periodic image (small boxes only)
           __builtin_nontemporal_store(static_cast<int>(ent), nb10 + row + slot);    // the three streams are written once and read by other kernels: past the L2, which holds the table nodes
         }
-#ifdef RXMD_EXPERIMENTS
-        if (!(g.probe & 16))
-#endif
+        if (!exp_probe_mask(g.probe, 16))
         __builtin_nontemporal_store(h, hess + row + slot);
         if (F32) __builtin_nontemporal_store(static_cast<float>(h), hess32 + row + slot);
       }
@@ -450,9 +442,7 @@ __global__ void __launch_bounds__(64 * L10_ROWS) k_list10(int N, int S10, Grid g
   __syncthreads();
   if (!rowlive) return;                            // (no barrier below)
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-#ifdef RXMD_EXPERIMENTS
-  if (g.probe == 1) { if (lane == 0) n10[i] = L; return; }
-#endif
+  if (exp_probe(g.probe, 1)) { if (lane == 0) n10[i] = L; return; }
   // The column of a candidate = the last one that starts at or before it.  Candidates are walked in order, so the wavefront keeps the next column
   // boundary it has not passed (tn, a scalar; the boundaries sit one per lane in myP and are read with v_readlane): a batch of 64 candidates
   // starts in column tn - 1 and a lane adds one for every boundary of the batch at or below its candidate -- 1.2 boundaries per batch on
@@ -617,7 +607,7 @@ void Engine::build_bonded_list(bool pack_only) {
 
 // The 4-byte entry stream nb10 (cell-sorted position | type | flags per entry: 1.7 GB per build at 980 k atoms) is written only for a build whose
 // kernels read it.  The window forms of the matrix pass and of ENbond read the 2-byte slots, and the hydrogen-bond sweep finds a donor row's partners
-// through the slots and the group's window (bonded.hip); the readers of the entries are the row forms (k_spmv, k_nonbond), the PQEq kernels, the
+// through the slots and the group's window (hbonds.hip); the readers of the entries are the row forms (k_spmv, k_nonbond), the PQEq kernels, the
 // self-image flag of small boxes and debug tap 11.  Decided on the host BEFORE the sweep, so from the previous build's windows: a build that loses
 // its windows after one that had them is swept again with the stream on (build_ghosts_and_lists), and require_nb10() does the same for a reader
 // that finds the stream missing -- from then on the engine always writes it.

@@ -1,6 +1,6 @@
 // pair_walk.h -- the walk over a resident's row of the 10 A list for kernels that only READ what k_list10 (lists.hip) left: the pair graph
 // (pair_graph.hip) and the structure statistics (structure.hip).  The two routes from an entry to the partner's cell-sorted position k are those
-// of k_ehb_sweep (bonded.hip): the 4-byte entry where the build wrote the stream (nb10_valid), else the 2-byte window slot: sl10 & 0x7fff ->
+// of k_ehb_sweep (hbonds.hip): the 4-byte entry where the build wrote the stream (nb10_valid), else the 2-byte window slot: sl10 & 0x7fff ->
 // win_k of the row's group (rpos[i] / WIN_ROWS) -> first position of the slot's unit + offset in the unit.  The partner is atom j = perm[k], its
 // position comes from the per-atom arrays (FORCE overwrites the w of the packed cell-sorted copy with charges).  Engine::pair_list fills the struct.
 #pragma once

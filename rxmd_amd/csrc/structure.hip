@@ -130,11 +130,6 @@ __global__ void __launch_bounds__(64 * SP_WAVES) k_struct_pairs(PairList L, Stru
 // ---- angles ----------------------------------------------------------------------------------------------------------------------------------
 struct AngleTile { double *ux, *uy, *uz; int *code; };        // one wavefront's tile in LDS; code = shell index << 16 | type << 8 | present number (0xff: none)
 
-__device__ inline void wave_lds_sync() {                       // what the lanes of this wavefront stored to LDS is visible to its other lanes
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // walks the whole row; the entries inside the largest shell get consecutive numbers in list order, those numbered [lo, lo + SA_TILE) are staged.
 // Returns how many the shell holds (wave-uniform)
 __device__ inline int stage_tile(const PairList &L, const StructArgs &A, const TypeMap &T, const PairRow &R, int lane, int lo, const AngleTile &S) {

@@ -246,7 +246,7 @@ def test_the_engine_is_untouched_and_the_call_repeats_its_bits():
       * PE and astr agree at the bound the suite uses for sums that FORCE forms with global atomics (test_gpu_parity: rtol = atol-scale 1e-12).  Both are
         such sums: the 14 energies (atomicAdd(pe + k, ...) in every energy kernel), and the stress accumulators -- k_stress_partial / k_stress_final add
         the virial in a fixed order, but INTO accumulators that ENbond's pair virial (nonbonded.hip: atomicAdd(pe + 16 + c, s), one per workgroup) and
-        the torsions' image terms (bonded.hip: atomicAdd(pe + 16.., t0 * F0)) have reached in scheduling order.  astr is compared relative to its
+        the torsions' image terms (torsions.hip: atomicAdd(pe + 16.., t0 * F0)) have reached in scheduling order.  astr is compared relative to its
         largest component: the order-dependent error of such a sum scales with its terms, and all six components are sums of r_a f_b terms of one scale.
         Each figure is printed; where two engines happen to produce the same bits that is printed too.
     On ONE engine, where bits are a statement about the VJP: get_energy before and after the VJP calls returns the same PE, kinetic energy and charge
